@@ -14,8 +14,14 @@ independent columns (columns shard) followed by one RCCL all-gather
 commitments -- weak scaling.
 
 The LAST stdout line (rank 0) is ONE compact strict-JSON record (< 4 KB, `compact_record`):
-metric = scalar-point ops / s over the whole job, plus
-  roofline      dominant kernel k_accumulate: algorithmic bytes per launch / its HIP-event duration
+metric = scalar-point ops / s over the whole job, `ms_per_step` = one timed step.  A plain run sets
+up, warms up (a fixed number of untimed calls of the timed shape, so that the K steps see
+sustained clocks, then the W warmup steps), times the K steps and prints that line; nothing else.
+--dump-outputs DIR writes the last timed step's commitments to DIR/commitments.npy (float64, one
+row of 32 bytes per rank); the inputs are the same in every run.
+
+With --full the run also carries, as it always did:
+  roofline    dominant kernel k_accumulate: algorithmic bytes per launch / its HIP-event duration
                 against 8 TB/s; `traffic` / `valu_busy` from the committed PMC passes; `alu_frac` =
                 the integer-ALU side (the binding bound) against the v_mad_u64_u32 issue rate
                 measured on THIS box in THIS run, `issue_frac` = the same for the loop's whole
@@ -23,11 +29,11 @@ metric = scalar-point ops / s over the whole job, plus
                 and lone call -- flat scalars only
   cpu_baseline  N = 1 only: the reference's own CPU backend (oracle/_ref) on THE SAME scalars; the
                 timed GPU commitment must equal its output or the bench aborts (`verified`)
-The full record (every leg, nested) goes to gpurun_out/bench_detail.json (--detail-file).  With
---detail the untimed legs that only feed that file run too: BASELINE configs 1, 3, 4, 5 at their
-stated shapes on one GPU (each with its roofline, a bounded cpu_baseline sample and a full-size
-parity check), the 50 Hz power / clock trace, the host-buffer (PCIe-inclusive) figures.  N > 1:
-config 4's 256 columns sharded over the ranks and config 2 row-split run by default.
+and the full record (every leg, nested) goes to the detail file (--detail-file).  With --detail
+(which implies --full) the untimed legs that only feed that file run too: BASELINE configs 1, 3, 4, 5
+at their stated shapes on one GPU (each with its roofline, a bounded cpu_baseline sample and a
+full-size parity check), the 50 Hz power / clock trace, the host-buffer (PCIe-inclusive) figures.
+N > 1 under --full: config 4's 256 columns sharded over the ranks and config 2 row-split.
 """
 import argparse
 import ctypes
@@ -61,21 +67,32 @@ HBM_PEAK_GBS = 8000.0
 SIMDS = 1024
 MAD_ISSUE_CYCLES = 4.0
 EFFECTIVE_CLOCK_HZ = 2.1e9  # refined from profiles/alu_calibration.json when present
+# a plain run's warm-up before its W warmup steps: this many calls of the timed shape in one
+# sequence, whatever K is (A/B against the parent's warm-up: profiles/plain_warmup_ab.json)
+PLAIN_WARMUP_CALLS = 60
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the reference-CPU baseline and the "
+                         "verification of the timed output against it, the roofline and stage times, "
+                         "the resident-generators, sustained and lone-call figures, N > 1 strong scaling, "
+                         "and the detail file; every option below but --log2n and "
+                         "--dry-run-one-gpu acts only under --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/*.npy "
+                         "(float64)")
     ap.add_argument("--log2n", type=int, default=None, help="override rows (debug only)")
     ap.add_argument("--no-cpu-baseline", action="store_true",
                     help="skip the reference-CPU leg (and with it the output verification)")
     ap.add_argument("--detail", action="store_true",
-                    help="also run the untimed legs that only feed the detail file: configs 1/3/4/5 at "
-                         "full shape, the 50 Hz device-state trace, the host-buffer (PCIe) figures, the "
-                         "one-process multi-device check (minutes; the default run is the headline, its "
-                         "roofline and the reference-CPU baseline)")
+                    help="implies --full, and also runs the untimed legs that only feed the detail "
+                         "file: configs 1/3/4/5 at full shape, the 50 Hz device-state trace, the "
+                         "host-buffer (PCIe) figures, the one-process multi-device check (minutes)")
     ap.add_argument("--detail-file", default=None,
                     help="where the full record goes (default gpurun_out/bench_detail.json beside "
                          "bench.py); the LAST stdout line is the compact record")
@@ -94,7 +111,13 @@ def parse_args():
                     help="self-test of the N > 1 control flow on a one-GPU box: every rank uses "
                          "cuda:0 and the collectives go through gloo on host copies (never a "
                          "measurement)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    args.full = args.full or args.detail
+    return args
 
 
 class Collectives:
@@ -977,7 +1000,12 @@ def compact_record(result):
 
 
 def emit(result, args):
-    """full record -> the detail file (and stderr); compact record -> the LAST line on stdout"""
+    """full record -> the detail file (and stderr) under --full; compact record -> the LAST line on
+    stdout"""
+    if not args.full:
+        sys.stdout.flush()
+        print(compact_record(result), flush=True)
+        return
     path = args.detail_file
     if path is None:
         path = os.path.join(ROOT, "gpurun_out", "bench_detail.json")
@@ -992,6 +1020,44 @@ def emit(result, args):
     sys.stderr.flush()
     sys.stdout.flush()
     print(compact_record(result), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (exact for bytes), at most 64 MB"""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {name: np.asarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes"
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def headline_record(args, world, n, name, elapsed):
+    """the record's headline members: what a plain run reports, and what --full reports beside its
+    other legs"""
+    return {
+        "metric": "MSM throughput (scalar-point ops/sec)",
+        "value": world * n * args.steps / elapsed,
+        "unit": "scalar-point ops/s",
+        "commitments_per_s": world * args.steps / elapsed,
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32 limbs (9 x 29-bit GF(2^255-19), v_mad_u64_u32 products)",
+        "data": "synthetic: std::mt19937{rank} bytes, uniform 252-bit scalars, generators "
+                "compute_base_element(i) supplied by the caller on every call"
+                + (" [DRY RUN: all ranks on one GPU, gloo collectives -- not a measurement]"
+                   if args.dry_run_one_gpu else ""),
+        "config": {"workload": name, "columns_per_gpu": 1, "rows": n,
+                   "parallelism": f"columns x{world}"},
+    }
 
 
 def main():
@@ -1030,7 +1096,9 @@ def main():
 
     lib = api.load()
     assert api.init(api.SXT_GPU_BACKEND, 0) == 0
-    # the untimed single-GPU legs that only feed the detail file run under --detail
+    # a plain run sets up, warms up, times the K steps and prints the headline; everything else
+    # runs under --full, and the untimed single-GPU legs that only feed the detail file under --detail
+    full = args.full
     aux_legs = args.detail and not args.no_aux
     config_legs = args.detail and not args.no_configs
     trace = SmiTrace() if (rank == 0 and world == 1 and aux_legs) else None
@@ -1038,7 +1106,7 @@ def main():
     # non-blocking tail streams: include/blitzar_amd.h, bzamd_pipeline_next)
     torch.cuda.set_stream(torch.cuda.Stream(device=dev))
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    oracle = None if args.no_cpu_baseline else load_oracle()
+    oracle = load_oracle() if full and not args.no_cpu_baseline else None
 
     # synthetic inputs, resident in HBM: per-rank scalar column (mt19937{rank}), shared generators
     scalars_host = wl.mt19937_scalars(1, n, nbytes, top_mask=top_mask, seed=rank)[0]
@@ -1089,7 +1157,7 @@ def main():
         legs["single_call_ms"] = 1e3 * (time.perf_counter() - t_single) / stage_steps
         legs["lone_output"] = out.cpu().numpy().copy()
 
-    handle = lib.bzamd_generators_new_device(curve_id, vp(generators), n, stream)
+    handle = lib.bzamd_generators_new_device(curve_id, vp(generators), n, stream) if full else None
     out2 = torch.zeros((1, 32), dtype=torch.uint8, device=dev)
 
     def resident_lone_pass():
@@ -1148,6 +1216,19 @@ def main():
         legs["sustained_calls"] = calls
         legs["untimed_calls_before_clock"] = legs.get("untimed_calls_before_clock", 0) + 2
 
+    def plain_warmup():
+        # the two calls that size the workspace of the timed call shape, then one sequence of
+        # PLAIN_WARMUP_CALLS of them: past the clock ramp described below, whatever K is
+        for k in range(2):
+            step(0)
+        finish()
+        torch.cuda.synchronize()
+        for k in range(PLAIN_WARMUP_CALLS):
+            step(k % max_steps)
+        finish()
+        torch.cuda.synchronize()
+        legs["untimed_calls_before_clock"] = 2 + PLAIN_WARMUP_CALLS
+
     # Order.  The device idles at ~100 MHz and comes back slowly: after ANY idle gap (20 ms are
     # enough) the first calls of a sequence take 1.14, 1.11, 1.06, 1.03, 1.00, 0.98 ms ... and the
     # sustained 0.96 only after ~30 ms of load (tools/prof/clock_course.py; sustained means
@@ -1156,10 +1237,14 @@ def main():
     # the legs that are long sequences in throughput mode run right before the W warmup steps --
     # the last of them with the timed region's own call shape, so that nothing is allocated between
     # it and the clock -- and the lone-call legs (low load: 40 % of a lone call is tails) after the
-    # timed region.
-    resident_sequence()
-    IN_RUN_ALU["before"] = probe_alu(lib)
-    long_sequence()
+    # timed region.  A plain run measures none of them: it warms up with the timed call shape
+    # alone, for a number of calls that does not depend on K (plain_warmup).
+    if full:
+        resident_sequence()
+        IN_RUN_ALU["before"] = probe_alu(lib)
+        long_sequence()
+    else:
+        plain_warmup()
 
     for k in range(args.warmup):
         step(k)
@@ -1172,9 +1257,10 @@ def main():
     # the timed region carries HIP events around the dominant kernel only (the roofline's live
     # duration), and around one launch in four: every recorded stage costs an event pair = two
     # stream bubbles per call (~1.5 % of a step when every call carries them); the other five
-    # stages are measured by a separate, untimed pass below
+    # stages are measured by a separate, untimed pass below.  Only under --full: a plain run times
+    # the steps alone.
     acc_sample = 4 if args.steps >= 8 else 1
-    clock = StageClock(lib, args.steps, ACCUMULATE_ONLY, sample_every=acc_sample)
+    clock = StageClock(lib, args.steps, ACCUMULATE_ONLY, sample_every=acc_sample) if full else None
     wall0 = time.time()
     t0 = time.perf_counter()
     for k in range(args.steps):
@@ -1187,6 +1273,27 @@ def main():
     elapsed = time.perf_counter() - t0
     if trace is not None:
         trace.window("timed_region", wall0, time.time())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the commitment of every
+        # rank's column (one row per rank), as bytes
+        last = args.steps - 1
+        commitments = (gathered.view(world, max_steps, 32)[:, last] if world > 1
+                       else outs[last:last + 1])
+        dump_outputs(args.dump_outputs, {"commitments": commitments.cpu().numpy()})
+    if not full:
+        if world > 1:
+            t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+            coll.all_reduce(t, dist.ReduceOp.MAX)
+            elapsed = float(t.item())
+        if rank == 0:
+            result = headline_record(args, world, n, name, elapsed)
+            result["effective_warmup_calls"] = legs["untimed_calls_before_clock"] + args.warmup
+            emit(result, args)
+        api.reset_for_testing()
+        if world > 1:
+            coll.barrier()
+            dist.destroy_process_group()
+        return
     timed_stages, calls = clock.collect(args.steps)
     IN_RUN_ALU["after"] = probe_alu(lib)
     all_outputs = outs[:args.steps].cpu().numpy()
@@ -1264,21 +1371,12 @@ def main():
         sharded = sharded_config4(lib, oracle, args, dev, stream, rank, world, dist, coll)
 
     if rank == 0:
-        ms_per_step = 1e3 * elapsed / args.steps
-        total_ops = world * n * args.steps
-        result = {
-            "metric": "MSM throughput (scalar-point ops/sec)",
-            "value": total_ops / elapsed,
-            "unit": "scalar-point ops/s",
-            "commitments_per_s": world * args.steps / elapsed,
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
+        result = headline_record(args, world, n, name, elapsed)
+        result.update({
             # calls of the timed shape (and of the resident-generators shape) issued right before
             # the W warmup steps to get the device out of its idle clocks (see "Order" above): the
             # timed region is a SUSTAINED-clock figure
             "effective_warmup_calls": legs["untimed_calls_before_clock"] + args.warmup,
-            "ms_per_step": ms_per_step,
             "single_call_ms": single_call_ms,
             "sustained_ms_per_step": legs["sustained_ms"],
             "sustained_steps": legs["sustained_calls"],
@@ -1289,17 +1387,7 @@ def main():
                     "`sustained_ms_per_step` = the same step over the last `sustained_steps` calls "
                     "of a longer sequence that runs right before the warmup steps (two events on "
                     "the caller's stream, flush included)",
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32 limbs (9 x 29-bit GF(2^255-19), v_mad_u64_u32 products)",
-            "data": "synthetic: std::mt19937{rank} bytes, uniform 252-bit scalars, generators "
-                    "compute_base_element(i) supplied by the caller on every call"
-                    + (" [DRY RUN: all ranks on one GPU, gloo collectives -- not a measurement]"
-                       if args.dry_run_one_gpu else ""),
-            "config": {"workload": name, "columns_per_gpu": 1, "rows": n,
-                       "parallelism": f"columns x{world}"},
-        }
+        })
         if verified:
             result["verified"] = verified
         if resident_ms is not None and world == 1:

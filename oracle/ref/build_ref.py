@@ -76,6 +76,29 @@ def compile_one(src):
     return obj
 
 
+def build_pins():
+    """the boundary pins of tests/test_boundary_pins.py that are compiled from the reference tree:
+    tests/native/boundary/signatures.cc against the reference's cbindings/blitzar_api.h (its twin
+    against include/blitzar_api.h is built by __graft_entry__.build()) and the reference's example
+    program example/cbindings1/main.cc, unchanged, both linked against libblitzar_amd.so"""
+    root = os.path.dirname(os.path.dirname(HERE))
+    lib_so = os.path.join(root, "blitzar_amd", "lib", "libblitzar_amd.so")
+    if not os.path.exists(lib_so):
+        print("[oracle/_ref] libblitzar_amd.so not built yet; boundary pins skipped")
+        return
+    pins = [("sig_ref", os.path.join(root, "tests", "native", "boundary", "signatures.cc"),
+             ["-I" + REF, '-DBZ_API_HEADER="cbindings/blitzar_api.h"']),
+            ("ref_example_cbindings1", os.path.join(REF, "example", "cbindings1", "main.cc"),
+             ["-I" + REF])]
+    for name, src, flags in pins:
+        exe = os.path.join(OUT, name)
+        if (not os.path.exists(exe)
+                or os.path.getmtime(exe) < max(os.path.getmtime(src), os.path.getmtime(lib_so))):
+            subprocess.run(["g++", "-O1", "-std=c++17", *flags, src, "-L" + os.path.dirname(lib_so),
+                            "-lblitzar_amd", "-Wl,-rpath,$ORIGIN/../../blitzar_amd/lib",
+                            "-Wl,-rpath,/opt/rocm/lib", "-o", exe], check=True)
+
+
 def main():
     if not os.path.isdir(REF):
         print(f"[oracle/_ref] {REF} not present; keeping prebuilt artefacts (if any)")
@@ -88,11 +111,13 @@ def main():
     if os.path.exists(lib) and all(os.path.getmtime(lib) >= os.path.getmtime(s)
                                    for s in srcs + drivers + shims + [__file__]):
         print(f"[oracle/_ref] up to date ({len(srcs)} reference TUs)")
+        build_pins()
         return 0
     with concurrent.futures.ThreadPoolExecutor(max_workers=os.cpu_count() or 4) as ex:
         objs = list(ex.map(compile_one, srcs + drivers))
     subprocess.run([CXX, "-shared", "-Wl,-z,defs", "-o", lib, *objs], check=True)
     print(f"[oracle/_ref] built {lib} from {len(srcs)} reference TUs")
+    build_pins()
     return 0
 
 

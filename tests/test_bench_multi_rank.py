@@ -20,8 +20,8 @@ def test_two_ranks_dry_run(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29617", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "4", "--warmup", "2", "--dry-run-one-gpu", "--no-cpu-baseline",
-           "--no-configs", "--detail-file", str(tmp_path / "detail.json")]
+           "--gpus", "2", "--steps", "4", "--warmup", "2", "--dry-run-one-gpu", "--full",
+           "--no-cpu-baseline", "--no-configs", "--detail-file", str(tmp_path / "detail.json")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _records(r.stdout, tmp_path / "detail.json")
@@ -61,7 +61,7 @@ def _dry_run(ranks, port, extra, timeout, tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(ranks), "--dry-run-one-gpu"] + extra
+           "--gpus", str(ranks), "--dry-run-one-gpu", "--full"] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     return _records(r.stdout, tmp_path / "detail.json")

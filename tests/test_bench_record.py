@@ -6,9 +6,12 @@ import importlib.util
 import io
 import json
 import os
+import subprocess
+import sys
 import types
 from contextlib import redirect_stdout
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -73,7 +76,7 @@ def test_compact_record_survives_nan_and_oversized_members(bench):
 
 def test_emit_prints_the_compact_record_last_and_writes_the_sidecar(bench, tmp_path):
     full = _canned()
-    args = types.SimpleNamespace(detail_file=str(tmp_path / "sub" / "detail.json"))
+    args = types.SimpleNamespace(detail_file=str(tmp_path / "sub" / "detail.json"), full=True)
     buf = io.StringIO()
     with redirect_stdout(buf):
         bench.emit(full, args)
@@ -105,3 +108,55 @@ def test_issue_frac_prices_the_whole_instruction_mix(bench):
     full["roofline"]["issue_frac"] = roof["issue_frac"]
     d = _strict(bench.compact_record(full))
     assert d["roofline"]["issue_frac"] == pytest.approx(roof["issue_frac"], rel=1e-5)
+
+
+def test_plain_and_full_options(bench):
+    """a plain run is the default; --detail implies --full; --steps sets the timed steps (>= 1)"""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert bench.parse_args(["--full"]).full and bench.parse_args(["--detail"]).full
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_plain_emit_prints_the_compact_record_and_writes_nothing(bench, tmp_path):
+    full = _canned()
+    args = types.SimpleNamespace(detail_file=str(tmp_path / "detail.json"), full=False)
+    buf = io.StringIO()
+    with redirect_stdout(buf):
+        bench.emit(full, args)
+    lines = buf.getvalue().splitlines()
+    assert len(lines) == 1 and len(lines[0]) < 4096
+    d = _strict(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert not (tmp_path / "detail.json").exists() and "detail_file" not in d
+
+
+def test_dump_outputs_are_float64_and_exact(bench, tmp_path):
+    c = np.arange(64, dtype=np.uint8).reshape(2, 32)
+    bench.dump_outputs(str(tmp_path / "d"), {"commitments": c})
+    got = np.load(tmp_path / "d" / "commitments.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, c)
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_commitment(oracle, tmp_path):
+    """a plain run at reduced rows prints the headline line only, and --dump-outputs holds the last
+    timed step's commitment: the reference CPU backend's on the same scalars and generators"""
+    log2n = 12
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
+           "--warmup", "1", "--log2n", str(log2n), "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _strict(r.stdout.splitlines()[-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["higher_is_better"] is True and "roofline" not in d and "cpu_baseline" not in d
+    got = np.load(tmp_path / "out" / "commitments.npy")
+    assert got.dtype == np.float64 and got.shape == (1, 32)
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import baseline_workloads as wl
+    scalars = wl.mt19937_scalars(1, 1 << log2n, 32, top_mask=0x0f, seed=0)[0]
+    want = oracle.commit(0, [(scalars, False)], oracle.ristretto_generators(1 << log2n))
+    assert np.array_equal(got, want.astype(np.float64))

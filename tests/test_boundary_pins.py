@@ -10,8 +10,9 @@
   * BLITZAR_LOG_LEVEL (sxt/base/log/setup.cc:28-65): `info` lines where the reference has them
     (cbindings/backend.cc:78,122,127, bucket_method2/multiexponentiation.h:55,71), nothing by default.
 
-__graft_entry__.build() compiles the binaries (the two that need /root/reference only where it is
-mounted; they travel to the GPU box prebuilt)."""
+__graft_entry__.build() compiles sig_ours into tests/native/_build/; the two compiled from the reference
+tree are built by the oracle's recipe (oracle/ref/build_ref.py, which build() runs) into oracle/_ref/
+(only where that tree is present; elsewhere they are used prebuilt, like the oracle itself)."""
 import os
 import re
 import subprocess
@@ -21,12 +22,13 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "tests", "native", "_build")
+REF_BUILD = os.path.join(ROOT, "oracle", "_ref")
 
 
 def _exe(name):
-    path = os.path.join(BUILD, name)
+    path = os.path.join(BUILD if name == "sig_ours" else REF_BUILD, name)
     if not os.path.exists(path):
-        pytest.skip(f"{name} not built (__graft_entry__.build(), /root/reference mounted)")
+        pytest.skip(f"{name} not built (__graft_entry__.build() with the reference tree present)")
     return path
 
 

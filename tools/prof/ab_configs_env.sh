@@ -7,7 +7,7 @@ mkdir -p $(dirname $OUT)
 for spec in "$@"; do
   envs=$spec; [ "$spec" = "-" ] && envs=""
   echo "== $spec" >> $OUT
-  env $(echo $envs | tr ',' ' ') timeout 600 python bench.py --steps 20 --warmup 3 2>&1 | tail -1 | python3 -c "
+  env $(echo $envs | tr ',' ' ') timeout 600 python bench.py --detail --steps 20 --warmup 3 2>&1 | tail -1 | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 print('cfg2 ms %.4f' % d['ms_per_step'], d['stage_ms'])

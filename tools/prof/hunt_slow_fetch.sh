@@ -26,5 +26,5 @@ P=tools/pipeline_bench/_build/pipeline_bench
   echo "== bls12-381 2^22"; $P --curve 1 --log2n 22 --steps 10 --warmup 2 | tail -1
   tools/ubench/bin/tail_latency 2>/dev/null | tail -30
 } > "$OUT/slow_box.log" 2>&1
-python3 bench.py --gpus 1 --steps 20 --warmup 5 --detail-file "$OUT/bench_detail.json" > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --gpus 1 --full --steps 20 --warmup 5 --detail-file "$OUT/bench_detail.json" > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -40 "$OUT/slow_box.log"
