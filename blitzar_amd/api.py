@@ -129,6 +129,18 @@ def load():
     lib.bzamd_generators_new_host.restype = vp
     lib.bzamd_generators_free.argtypes = [vp]
     lib.bzamd_generators_free.restype = None
+    lib.bzamd_compute_commitments_with_generator_offsets.argtypes = [
+        cu, vp, u32, ctypes.POINTER(sxt_sequence_descriptor), vp, u64, ctypes.POINTER(u64)]
+    lib.bzamd_compute_commitments_with_generator_offsets.restype = None
+    lib.bzamd_curve25519_compute_commitments_with_offsets.argtypes = [
+        vp, u32, ctypes.POINTER(sxt_sequence_descriptor), ctypes.POINTER(u64)]
+    lib.bzamd_curve25519_compute_commitments_with_offsets.restype = None
+    lib.bzamd_msm_device_offsets.argtypes = [cu, vp, u32, ctypes.POINTER(sxt_sequence_descriptor),
+                                             vp, u64, ctypes.POINTER(u64), vp]
+    lib.bzamd_msm_device_offsets.restype = None
+    lib.bzamd_msm_device_resident_offsets.argtypes = [
+        vp, u32, ctypes.POINTER(sxt_sequence_descriptor), vp, ctypes.POINTER(u64), vp]
+    lib.bzamd_msm_device_resident_offsets.restype = None
     lib.bzamd_msm_device_resident.argtypes = [vp, u32, ctypes.POINTER(sxt_sequence_descriptor),
                                               vp, vp]
     lib.bzamd_msm_device_resident.restype = None
@@ -223,6 +235,34 @@ def compute_pedersen_commitments(curve_id, columns, generators=None, offset_gene
     }[curve_id]
     gens = np.ascontiguousarray(generators)
     fn(_ptr(out), num, descs, _ptr(gens))
+    return out
+
+
+def offsets_array(offsets, num_columns):
+    """per-column generator offsets -> (ctypes u64 pointer or None, keep-alive array)"""
+    if offsets is None:
+        return None, None
+    arr = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    assert arr.shape[0] == num_columns, "one generator offset per column"
+    return arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), arr
+
+
+def compute_commitments_with_generator_offsets(curve_id, columns, generators, offsets):
+    """commitments[i] = sum_j scalar_ij * G[offsets[i] + j] with host buffers (either backend).
+    `generators`: uint8 array in the C-ABI layout of the curve (its rows are the sequence G), or None
+    for the built-in ristretto generators; `offsets`: one per column, or None (all 0)."""
+    lib = load()
+    descs, keep = make_descriptors(columns)
+    num = len(keep)
+    out = np.zeros((num, CURVE_LAYOUT[curve_id][1]), dtype=np.uint8)
+    offs, _keep_offs = offsets_array(offsets, num)
+    if generators is None:
+        assert curve_id == SXT_CURVE_RISTRETTO255, "built-in generators are ristretto255 only"
+        lib.bzamd_curve25519_compute_commitments_with_offsets(_ptr(out), num, descs, offs)
+        return out
+    gens = np.ascontiguousarray(generators)
+    lib.bzamd_compute_commitments_with_generator_offsets(curve_id, _ptr(out), num, descs,
+                                                         _ptr(gens), gens.shape[0], offs)
     return out
 
 

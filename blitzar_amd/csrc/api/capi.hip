@@ -119,6 +119,9 @@ void host_builtin_generators(api_state& st, ed_point* out, u64 n, u64 offset) {
 struct checked_columns {
   std::vector<host_column> cols;
   u64 longest = 0;
+  // generators the call reads, from its first one: max over columns of generator_offset + n (the
+  // longest column unless the call has per-column generator offsets)
+  u64 generator_rows = 0;
   size_t total_bytes = 0;
 };
 
@@ -142,7 +145,28 @@ checked_columns check_descriptors(const sxt_sequence_descriptor* descriptors, u3
     r.longest = std::max<u64>(r.longest, d.n);
     r.total_bytes += device_arena::padded(static_cast<size_t>(d.n) * d.element_nbytes + 32);
   }
+  r.generator_rows = r.longest;
   return r;
+}
+
+// Per-column generator offsets (the bzamd_*_offsets entry points): row r of column i is paired with
+// generator offsets[i] + r of a sequence of `num_generators` (nullptr: every offset is 0).  A column
+// that reaches past the sequence aborts, like a bad descriptor.  The columns' offsets are made
+// relative to the lowest one, which is returned: the call reads generators [lowest, lowest +
+// cc.generator_rows) and nothing outside them is uploaded or converted.
+u64 apply_generator_offsets(checked_columns& cc, const u64* offsets, u64 num_generators) {
+  u64 lowest = ~u64{0};
+  for (size_t i = 0; i < cc.cols.size(); ++i) {
+    const u64 off = offsets != nullptr ? offsets[i] : 0;
+    BZ_RELEASE_ASSERT(off <= num_generators && cc.cols[i].n <= num_generators - off,
+                      "generator offset + sequence length exceeds the number of generators");
+    cc.cols[i].generator_offset = off;
+    if (cc.cols[i].n != 0) lowest = std::min(lowest, off);
+  }
+  if (lowest == ~u64{0}) lowest = 0; // every column is empty
+  for (auto& c : cc.cols) c.generator_offset = c.n != 0 ? c.generator_offset - lowest : 0;
+  cc.generator_rows = generator_rows_of(cc.cols);
+  return lowest;
 }
 
 enum class generator_source { host_api, builtin };
@@ -263,14 +287,19 @@ size_t row_split_parts(size_t shards, u64 longest) {
   return static_cast<size_t>(std::min<u64>(shards, std::max<u64>(1, longest / 1024)));
 }
 
-// rows [row_begin, row_end) of every column (columns shorter than the range keep what they have)
+// the rows of every column that meet generators [row_begin, row_end) of the call, with generator
+// offsets relative to row_begin (without offsets: rows [row_begin, row_end) of every column, columns
+// shorter than the range keep what they have)
 std::vector<host_column> row_range_of(const std::vector<host_column>& cols, u64 row_begin,
                                       u64 row_end) {
   std::vector<host_column> mine = cols;
   for (auto& c : mine) {
-    const u64 b = std::min<u64>(row_begin, c.n), e = std::min<u64>(row_end, c.n);
+    const u64 first = c.generator_offset, last = c.generator_offset + c.n;
+    const u64 b = std::min(std::max(row_begin, first), last) - first;
+    const u64 e = std::min(std::max(row_end, first), last) - first;
     c.data = c.data == nullptr ? nullptr : c.data + b * c.row_stride;
     c.n = e - b;
+    c.generator_offset = c.n != 0 ? first + b - row_begin : 0;
   }
   return mine;
 }
@@ -299,10 +328,18 @@ std::atomic<u64> g_max_rows_per_pass{u64{1} << 28};
 // uploaded in chunks on a copy stream while the engine works on the previous chunk (the DMA
 // engines and the CUs are independent): the reference benchmark's 10 x 2^20 x 32-byte job spends a
 // third of its time in H2D copies otherwise.
+// `longest` = the generators the columns read from `gens` on (generator_rows_of(cols)).
 u8* enqueue_commitments(api_state& st, device_state& ds, const curve_vtable& vt,
                         std::vector<host_column> cols, u64 longest, const generator_ref& gens,
                         u32 out_stride, bool projective_out, std::vector<hipEvent_t>& events) {
   ds.activate();
+  // the per-call window table lives in the context until the next build: nothing of another
+  // thread (bzamd_msm_device* takes no device lease) may enqueue between its build and our last chunk
+  struct context_hold {
+    msm_context* ctx;
+    explicit context_hold(msm_context* c) : ctx(c) { msm_context_hold(c); }
+    ~context_hold() { msm_context_release(ctx); }
+  } hold{ds.ctx};
   size_t total_bytes = 0;
   for (const auto& c : cols) {
     total_bytes += device_arena::padded(static_cast<size_t>(c.n) * c.row_stride + 32);
@@ -694,12 +731,23 @@ bool shards_over_devices(const api_state& st, const checked_columns& cc) {
 // (the call stays on that device) or, with `single` == nullptr, of every device (the call may
 // shard).  Sequences of more than one pass fold their partials on devices[0]: `single` must be that
 // device then (compute_commitments sees to it).
+// `generator_offsets` (nullptr: all 0) / `num_generators`: per-column windows of the generator
+// sequence (apply_generator_offsets).
 void compute_commitments_locked(api_state& st, const curve_vtable& vt, void* commitments,
                                 u32 num_sequences, const sxt_sequence_descriptor* descriptors,
                                 const void* generators, generator_source source,
                                 u64 offset_generators, bool projective_out,
-                                device_state* single) {
+                                device_state* single, const u64* generator_offsets = nullptr,
+                                u64 num_generators = ~u64{0}) {
   checked_columns cc = check_descriptors(descriptors, num_sequences);
+  {
+    const u64 lowest = apply_generator_offsets(cc, generator_offsets, num_generators);
+    if (source == generator_source::host_api) {
+      if (generators != nullptr) generators = static_cast<const u8*>(generators) + vt.api_generator_size * lowest;
+    } else {
+      offset_generators += lowest;
+    }
+  }
   const u32 out_stride = static_cast<u32>(projective_out ? vt.projective_size : vt.output_size);
 
   size_t scalar_bytes = 0;
@@ -710,8 +758,8 @@ void compute_commitments_locked(api_state& st, const curve_vtable& vt, void* com
     std::vector<ed_point> builtin;
     const u8* gens = static_cast<const u8*>(generators);
     if (source == generator_source::builtin) {
-      builtin.resize(cc.longest);
-      host_builtin_generators(st, builtin.data(), cc.longest, offset_generators);
+      builtin.resize(cc.generator_rows);
+      host_builtin_generators(st, builtin.data(), cc.generator_rows, offset_generators);
       gens = reinterpret_cast<const u8*>(builtin.data());
     }
     // BLITZAR_AMD_FORCE_SHARDS on the host backend: the same split rules as the GPU backend below,
@@ -720,24 +768,23 @@ void compute_commitments_locked(api_state& st, const curve_vtable& vt, void* com
     const size_t shards = st.host_shards;
     if (shards < 2 || projective_out || scalar_bytes < g_shard_min_bytes.load() ||
         cc.longest == 0) {
-      vt.msm_host(out, out_stride, projective_out, cc.cols, gens, false, cc.longest);
+      vt.msm_host(out, out_stride, projective_out, cc.cols, gens, false, cc.generator_rows);
     } else if (num_sequences >= shards) {
       const std::vector<unit_range> ranges = split_by_weight(column_weights(cc.cols), shards);
       run_on_devices(shards, [&](size_t k) {
         const unit_range r = ranges[k];
         if (r.begin == r.end) return;
         const std::vector<host_column> mine(cc.cols.begin() + r.begin, cc.cols.begin() + r.end);
-        u64 longest = 0;
-        for (const auto& c : mine) longest = std::max<u64>(longest, c.n);
         vt.msm_host(out + r.begin * static_cast<size_t>(out_stride), out_stride, false, mine, gens,
-                    false, longest);
+                    false, generator_rows_of(mine));
       });
     } else {
-      const size_t parts = row_split_parts(shards, cc.longest);
+      const size_t parts = row_split_parts(shards, cc.generator_rows);
       const size_t psize = vt.projective_size;
       std::vector<u8> partials(psize * num_sequences * parts);
       run_on_devices(parts, [&](size_t k) {
-        const u64 row_begin = cc.longest * k / parts, row_end = cc.longest * (k + 1) / parts;
+        const u64 row_begin = cc.generator_rows * k / parts;
+        const u64 row_end = cc.generator_rows * (k + 1) / parts;
         const std::vector<host_column> mine = row_range_of(cc.cols, row_begin, row_end);
         vt.msm_host(partials.data() + psize * num_sequences * k, static_cast<u32>(psize), true,
                     mine, gens + vt.api_generator_size * row_begin, false, row_end - row_begin);
@@ -760,7 +807,7 @@ void compute_commitments_locked(api_state& st, const curve_vtable& vt, void* com
   const generator_ref all_gens{source, generators, offset_generators};
   // sequences longer than one pass of the engine: row ranges, like the row split below
   const u64 max_rows = g_max_rows_per_pass.load();
-  const size_t passes = static_cast<size_t>((cc.longest + max_rows - 1) / max_rows);
+  const size_t passes = static_cast<size_t>((cc.generator_rows + max_rows - 1) / max_rows);
 
   if (!shard && passes <= 1) {
     device_state& ds = single != nullptr ? *single : st.primary();
@@ -769,21 +816,22 @@ void compute_commitments_locked(api_state& st, const curve_vtable& vt, void* com
     // are resident when the call lies inside the init-time cache
     const bool cached_builtin = source == generator_source::builtin &&
                                 offset_generators <= st.host_generators.size() &&
-                                cc.longest <= st.host_generators.size() - offset_generators &&
+                                cc.generator_rows <= st.host_generators.size() - offset_generators &&
                                 ds.builtin.d_addends != nullptr;
     generator_ref call_gens = all_gens;
     if (source == generator_source::host_api) {
-      call_gens.cached = cached_caller_generators(st, ds, vt, generators, cc.longest);
+      call_gens.cached = cached_caller_generators(st, ds, vt, generators, cc.generator_rows);
     }
     row_pipeline_shape shape;
     if (call_gens.cached == nullptr && (source == generator_source::host_api || cached_builtin)) {
-      shape = choose_row_chunks(vt, cc.cols, cc.longest, source == generator_source::host_api);
+      shape = choose_row_chunks(vt, cc.cols, cc.generator_rows, source == generator_source::host_api);
     }
     u8* d_out = shape.chunks > 1
-                    ? enqueue_commitments_row_pipeline(st, ds, vt, cc.cols, cc.longest, call_gens,
-                                                       out_stride, projective_out, shape, events)
-                    : enqueue_commitments(st, ds, vt, cc.cols, cc.longest, call_gens, out_stride,
-                                          projective_out, events);
+                    ? enqueue_commitments_row_pipeline(st, ds, vt, cc.cols, cc.generator_rows,
+                                                       call_gens, out_stride, projective_out, shape,
+                                                       events)
+                    : enqueue_commitments(st, ds, vt, cc.cols, cc.generator_rows, call_gens,
+                                          out_stride, projective_out, events);
     BZ_HIP_CHECK(hipMemcpyAsync(out, d_out, static_cast<size_t>(out_stride) * num_sequences,
                                 hipMemcpyDeviceToHost, ds.stream));
     BZ_HIP_CHECK(hipStreamSynchronize(ds.stream));
@@ -804,10 +852,20 @@ void compute_commitments_locked(api_state& st, const curve_vtable& vt, void* com
       if (r.begin == r.end) return;
       device_state& ds = *st.devices[k];
       std::vector<host_column> mine(cc.cols.begin() + r.begin, cc.cols.begin() + r.end);
-      u64 longest = 0;
-      for (const auto& c : mine) longest = std::max<u64>(longest, c.n);
+      // the device's window of the generators: from its columns' lowest offset on
+      u64 lowest = ~u64{0};
+      for (const auto& c : mine) lowest = c.n != 0 ? std::min(lowest, c.generator_offset) : lowest;
+      if (lowest == ~u64{0}) lowest = 0;
+      for (auto& c : mine) c.generator_offset = c.n != 0 ? c.generator_offset - lowest : 0;
+      generator_ref g = all_gens;
+      if (g.source == generator_source::host_api) {
+        g.host_generators = static_cast<const u8*>(generators) + vt.api_generator_size * lowest;
+      } else {
+        g.offset += lowest;
+      }
+      const u64 rows = generator_rows_of(mine);
       std::vector<hipEvent_t> events;
-      u8* d_out = enqueue_commitments(st, ds, vt, std::move(mine), longest, all_gens, out_stride,
+      u8* d_out = enqueue_commitments(st, ds, vt, std::move(mine), rows, g, out_stride,
                                       projective_out, events);
       BZ_HIP_CHECK(hipMemcpyAsync(out + r.begin * static_cast<size_t>(out_stride), d_out,
                                   static_cast<size_t>(out_stride) * (r.end - r.begin),
@@ -822,7 +880,7 @@ void compute_commitments_locked(api_state& st, const curve_vtable& vt, void* com
   // row split: over the devices, and / or into passes of at most max_rows rows (a device takes
   // every workers-th part, one after the other)
   const u32 psize = static_cast<u32>(vt.projective_size);
-  const size_t parts = std::max(row_split_parts(shard ? num_devices : 1, cc.longest), passes);
+  const size_t parts = std::max(row_split_parts(shard ? num_devices : 1, cc.generator_rows), passes);
   const size_t workers = shard ? std::min(num_devices, parts) : 1;
   device_state& root = st.primary();
   root.activate();
@@ -835,8 +893,10 @@ void compute_commitments_locked(api_state& st, const curve_vtable& vt, void* com
   run_on_devices(workers, [&](size_t w) {
     device_state& ds = *st.devices[w];
     for (size_t k = w; k < parts; k += workers) {
-      const u64 row_begin = static_cast<u64>(static_cast<unsigned __int128>(cc.longest) * k / parts);
-      const u64 row_end = static_cast<u64>(static_cast<unsigned __int128>(cc.longest) * (k + 1) / parts);
+      const u64 row_begin =
+          static_cast<u64>(static_cast<unsigned __int128>(cc.generator_rows) * k / parts);
+      const u64 row_end =
+          static_cast<u64>(static_cast<unsigned __int128>(cc.generator_rows) * (k + 1) / parts);
       std::vector<host_column> mine = row_range_of(cc.cols, row_begin, row_end);
       generator_ref g = all_gens;
       if (g.source == generator_source::host_api) {
@@ -880,7 +940,8 @@ long env_count(const char* name, long fallback) {
 void compute_commitments(const curve_vtable& vt, void* commitments, u32 num_sequences,
                          const sxt_sequence_descriptor* descriptors, const void* generators,
                          generator_source source, u64 offset_generators,
-                         bool projective_out = false) {
+                         bool projective_out = false, const u64* generator_offsets = nullptr,
+                         u64 num_generators = ~u64{0}) {
   if (num_sequences == 0) return; // reference: returns before touching anything
   BZ_RELEASE_ASSERT(commitments != nullptr, "commitments is null");
   api_state& st = state();
@@ -901,21 +962,25 @@ void compute_commitments(const curve_vtable& vt, void* commitments, u32 num_sequ
   } logged{num_sequences, descriptors};
   if (st.backend != SXT_GPU_BACKEND) { // the host backend keeps no per-call state: no lock
     compute_commitments_locked(st, vt, commitments, num_sequences, descriptors, generators, source,
-                               offset_generators, projective_out, nullptr);
+                               offset_generators, projective_out, nullptr, generator_offsets,
+                               num_generators);
     return;
   }
   // which devices the call needs is a function of its shapes alone
-  const checked_columns cc = check_descriptors(descriptors, num_sequences);
-  const bool several_passes = cc.longest > g_max_rows_per_pass.load();
+  checked_columns cc = check_descriptors(descriptors, num_sequences);
+  (void)apply_generator_offsets(cc, generator_offsets, num_generators);
+  const bool several_passes = cc.generator_rows > g_max_rows_per_pass.load();
   const current_device_guard restore_callers_device; // the call may run on any device (lease_any)
   if (shards_over_devices(st, cc)) {
     api_state::device_lease lease = st.lease_all();
     compute_commitments_locked(st, vt, commitments, num_sequences, descriptors, generators, source,
-                               offset_generators, projective_out, nullptr);
+                               offset_generators, projective_out, nullptr, generator_offsets,
+                               num_generators);
   } else {
     api_state::device_lease lease = several_passes ? st.lease(st.primary()) : st.lease_any();
     compute_commitments_locked(st, vt, commitments, num_sequences, descriptors, generators, source,
-                               offset_generators, projective_out, lease.device);
+                               offset_generators, projective_out, lease.device, generator_offsets,
+                               num_generators);
   }
 }
 
@@ -1685,15 +1750,18 @@ void msm_device_in_passes(const curve_vtable& vt, msm_context* ctx, u8* out, boo
                           const checked_columns& cc, const void* d_addends, size_t addend_size,
                           const void* d_api_generators, hipStream_t stream) {
   const u64 max_rows = g_max_rows_per_pass.load();
-  const size_t passes = static_cast<size_t>((cc.longest + max_rows - 1) / max_rows);
+  const size_t passes = static_cast<size_t>((cc.generator_rows + max_rows - 1) / max_rows);
   const u32 psize = static_cast<u32>(vt.projective_size);
   const u32 num_sequences = static_cast<u32>(cc.cols.size());
   const size_t partial_bytes = static_cast<size_t>(psize) * num_sequences;
   u8* d_partials = nullptr;
   BZ_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&d_partials), partial_bytes * passes, stream));
+  // (the passes cut the generator axis: a column with an offset meets the passes its window spans)
   for (size_t k = 0; k < passes; ++k) {
-    const u64 row_begin = static_cast<u64>(static_cast<unsigned __int128>(cc.longest) * k / passes);
-    const u64 row_end = static_cast<u64>(static_cast<unsigned __int128>(cc.longest) * (k + 1) / passes);
+    const u64 row_begin =
+        static_cast<u64>(static_cast<unsigned __int128>(cc.generator_rows) * k / passes);
+    const u64 row_end =
+        static_cast<u64>(static_cast<unsigned __int128>(cc.generator_rows) * (k + 1) / passes);
     const std::vector<host_column> mine = row_range_of(cc.cols, row_begin, row_end);
     if (d_addends != nullptr) {
       vt.msm_resident(*ctx, d_partials + partial_bytes * k, psize, true, mine,
@@ -1712,9 +1780,11 @@ void msm_device_in_passes(const curve_vtable& vt, msm_context* ctx, u8* out, boo
   BZ_HIP_CHECK(hipFreeAsync(d_partials, stream));
 }
 
+// `generator_offsets` (nullptr: all 0) / `num_generators`: apply_generator_offsets
 void msm_device(unsigned curve_id, void* out, uint32_t num_sequences,
                 const struct sxt_sequence_descriptor* descriptors, const void* generators,
-                void* stream, bool projective_out) {
+                void* stream, bool projective_out, const u64* generator_offsets = nullptr,
+                u64 num_generators = ~u64{0}) {
   if (num_sequences == 0) return;
   const curve_vtable* vt = curve_vtable_for(curve_id);
   BZ_RELEASE_ASSERT(vt != nullptr, "unknown curve id");
@@ -1723,7 +1793,9 @@ void msm_device(unsigned curve_id, void* out, uint32_t num_sequences,
   api_state& st = state();
   BZ_RELEASE_ASSERT(st.backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
   checked_columns cc = check_descriptors(descriptors, num_sequences);
-  if (cc.longest > g_max_rows_per_pass.load()) {
+  generators = static_cast<const u8*>(generators) +
+               vt->api_generator_size * apply_generator_offsets(cc, generator_offsets, num_generators);
+  if (cc.generator_rows > g_max_rows_per_pass.load()) {
     t_pipeline_next = false; // a call of several passes completes on the caller's stream
     msm_device_in_passes(*vt, st.context_for_current_device(), static_cast<u8*>(out),
                          projective_out, cc, nullptr, 0, generators,
@@ -1994,9 +2066,11 @@ void bzamd_generators_free(struct bzamd_generators* gens) {
   delete g;
 }
 
-void bzamd_msm_device_resident(void* commitments, uint32_t num_sequences,
-                               const struct sxt_sequence_descriptor* descriptors,
-                               const struct bzamd_generators* gens, void* stream) {
+namespace {
+void msm_device_resident(void* commitments, uint32_t num_sequences,
+                         const struct sxt_sequence_descriptor* descriptors,
+                         const struct bzamd_generators* gens, void* stream,
+                         const u64* generator_offsets) {
   if (num_sequences == 0) return;
   const auto* g = reinterpret_cast<const resident_generators*>(gens);
   BZ_RELEASE_ASSERT(g != nullptr, "generators handle is null");
@@ -2005,17 +2079,66 @@ void bzamd_msm_device_resident(void* commitments, uint32_t num_sequences,
   BZ_RELEASE_ASSERT(st.backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
   checked_columns cc = check_descriptors(descriptors, num_sequences);
   BZ_RELEASE_ASSERT(cc.longest <= g->n, "sequence longer than the resident generator set");
-  if (cc.longest > g_max_rows_per_pass.load()) {
+  // (the window-table slices stay `stride` apart from the set's row `lowest` on: a merged entry
+  // w * stride + row_base + row lands on slice w, generator lowest + row_base + row < n <= stride)
+  const u64 lowest = apply_generator_offsets(cc, generator_offsets, g->n);
+  const void* d_addends = g->table.rows_from(lowest, g->vt->resident_addend_size);
+  if (cc.generator_rows > g_max_rows_per_pass.load()) {
     t_pipeline_next = false;
     msm_device_in_passes(*g->vt, st.context_for_current_device(), static_cast<u8*>(commitments),
-                         false, cc, g->table.d_addends, g->vt->resident_addend_size, nullptr,
+                         false, cc, d_addends, g->vt->resident_addend_size, nullptr,
                          static_cast<hipStream_t>(stream));
     return;
   }
   apply_pipeline_request(st.context_for_current_device());
   g->vt->msm_resident(*st.context_for_current_device(), static_cast<u8*>(commitments),
-                      static_cast<u32>(g->vt->output_size), false, cc.cols, g->table.d_addends,
+                      static_cast<u32>(g->vt->output_size), false, cc.cols, d_addends,
                       static_cast<hipStream_t>(stream), g->table.tables());
+}
+} // namespace
+
+void bzamd_msm_device_resident(void* commitments, uint32_t num_sequences,
+                               const struct sxt_sequence_descriptor* descriptors,
+                               const struct bzamd_generators* gens, void* stream) {
+  msm_device_resident(commitments, num_sequences, descriptors, gens, stream, nullptr);
+}
+
+//--------------------------------------------------------------------------------------------------
+// per-column generator offsets: commitments[i] = sum_j scalar_ij G[generator_offsets[i] + j]
+//--------------------------------------------------------------------------------------------------
+void bzamd_msm_device_resident_offsets(void* commitments, uint32_t num_sequences,
+                                       const struct sxt_sequence_descriptor* descriptors,
+                                       const struct bzamd_generators* gens,
+                                       const uint64_t* generator_offsets, void* stream) {
+  msm_device_resident(commitments, num_sequences, descriptors, gens, stream, generator_offsets);
+}
+
+void bzamd_msm_device_offsets(unsigned curve_id, void* commitments, uint32_t num_sequences,
+                              const struct sxt_sequence_descriptor* descriptors,
+                              const void* generators, uint64_t num_generators,
+                              const uint64_t* generator_offsets, void* stream) {
+  msm_device(curve_id, commitments, num_sequences, descriptors, generators, stream, false,
+             generator_offsets, num_generators);
+}
+
+void bzamd_compute_commitments_with_generator_offsets(
+    unsigned curve_id, void* commitments, uint32_t num_sequences,
+    const struct sxt_sequence_descriptor* descriptors, const void* generators,
+    uint64_t num_generators, const uint64_t* generator_offsets) {
+  const curve_vtable* vt = curve_vtable_for(curve_id);
+  BZ_RELEASE_ASSERT(vt != nullptr, "unknown curve id");
+  if (num_sequences == 0) return;
+  BZ_RELEASE_ASSERT(generators != nullptr, "generators is null");
+  compute_commitments(*vt, commitments, num_sequences, descriptors, generators,
+                      generator_source::host_api, 0, false, generator_offsets, num_generators);
+}
+
+void bzamd_curve25519_compute_commitments_with_offsets(
+    struct sxt_ristretto255_compressed* commitments, uint32_t num_sequences,
+    const struct sxt_sequence_descriptor* descriptors, const uint64_t* generator_offsets) {
+  // the built-in sequence has no end: only offset + n must not wrap
+  compute_commitments(curve25519_vtable(), commitments, num_sequences, descriptors, nullptr,
+                      generator_source::builtin, 0, false, generator_offsets);
 }
 
 void bzamd_generator_multiples_device(unsigned curve_id, void* generators, const void* base,

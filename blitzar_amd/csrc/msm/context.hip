@@ -235,11 +235,11 @@ void msm_context_set_segments(msm_context* ctx, u32 log2_entries_per_accumulate_
 void msm_context_set_window_bits(msm_context* ctx, u32 window_bits) {
   BZ_RELEASE_ASSERT(window_bits == 0 || (window_bits >= 2 && window_bits <= 16),
                     "window width must be 2..16 (0 = automatic)");
-  std::lock_guard<std::mutex> lock(ctx->mu);
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   ctx->tuning.force_window_bits = window_bits;
 }
 u64 msm_context_set_call_tables(msm_context* ctx, int mode) {
-  std::lock_guard<std::mutex> lock(ctx->mu);
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   if (mode >= 0) {
     BZ_RELEASE_ASSERT(mode <= 1 || (mode >= static_cast<int>(kCallTableMinBits) &&
                                     mode <= static_cast<int>(kCallTableMaxBits)),
@@ -249,21 +249,23 @@ u64 msm_context_set_call_tables(msm_context* ctx, int mode) {
   }
   return ctx->call_tables_built;
 }
+void msm_context_hold(msm_context* ctx) { ctx->mu.lock(); }
+void msm_context_release(msm_context* ctx) { ctx->mu.unlock(); }
 void msm_context_defer_next_tail(msm_context* ctx) {
-  std::lock_guard<std::mutex> lock(ctx->mu);
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   ctx->defer_tail = true;
 }
 void msm_context_join_tail(msm_context* ctx, hipStream_t stream) {
-  std::lock_guard<std::mutex> lock(ctx->mu);
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   ctx->join_all(stream);
 }
 void msm_context_timing_begin(msm_context* ctx, size_t max_calls, unsigned stage_mask,
                               size_t sample_every) {
-  std::lock_guard<std::mutex> lock(ctx->mu);
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   ctx->timer.begin(max_calls, stage_mask & 0x3f, sample_every);
 }
 size_t msm_context_timing_collect(msm_context* ctx, double out_ms[6]) {
-  std::lock_guard<std::mutex> lock(ctx->mu);
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   return ctx->timer.collect(out_ms);
 }
 } // namespace bz

@@ -177,7 +177,7 @@ template <class C, class R = C, class H = C> struct curve_tu {
                            const std::vector<host_column>& cols, const void* d_addends,
                            hipStream_t stream, const window_table* tables) {
     if (cols.empty()) return;
-    std::lock_guard<std::mutex> lock(ctx.mu);
+    std::lock_guard<std::recursive_mutex> lock(ctx.mu);
     configure_sort_kernels(ctx);
     ctx.order_after_previous(stream);
     // (a forced per-call table -- tests, A/B runs -- merges whatever the cost model says)
@@ -279,15 +279,16 @@ template <class C, class R = C, class H = C> struct curve_tu {
         choose_call_table(cols, ctx.tuning, sizeof(typename R::addend), R::call_table_entry_cost,
                           ctx.force_call_table_bits);
     if (ch.shape.windows == 0) return nullptr;
-    u64 n = 0;
-    for (const auto& c : cols) n = c.n > n ? c.n : n;
+    // every generator the columns read (their windows' union; the longest column when all offsets
+    // are 0)
+    const u64 n = generator_rows_of(cols);
     shape = ch.shape;
     return build_call_table(ctx, d_api_generators, n, shape, stream);
   }
   static const void* call_table(msm_context& ctx, const std::vector<host_column>& cols,
                                 const void* d_api_generators, window_table* shape,
                                 hipStream_t stream) {
-    std::lock_guard<std::mutex> lock(ctx.mu);
+    std::lock_guard<std::recursive_mutex> lock(ctx.mu);
     ctx.order_after_previous(stream);
     const void* table = call_table_locked(ctx, cols, d_api_generators, *shape, stream);
     if (table != nullptr) ctx.mark_enqueued(stream);
@@ -297,7 +298,7 @@ template <class C, class R = C, class H = C> struct curve_tu {
                   const std::vector<host_column>& cols, const void* d_addends,
                   const void* d_api_generators, hipStream_t stream) {
     if (cols.empty()) return;
-    std::lock_guard<std::mutex> lock(ctx.mu);
+    std::lock_guard<std::recursive_mutex> lock(ctx.mu);
     configure_sort_kernels(ctx);
     ctx.order_after_previous(stream);
     // many columns over the same caller generators (the reference's bucket_method2 regime): the

@@ -104,6 +104,11 @@ void msm_context_set_window_bits(msm_context* ctx, u32 window_bits);
 // per-call window tables (engine.h, msm_context): mode 0 = the cost model decides (default), 1 = never,
 // 6..16 = a table of that width for every call with caller generators; returns the tables built so far
 u64 msm_context_set_call_tables(msm_context* ctx, int mode);
+// hold the context's mutex across several engine calls of one entry point (recursive: the calls
+// take it again), so that no other thread's call lands between a per-call window table's build and
+// the chunks that read it
+void msm_context_hold(msm_context* ctx);
+void msm_context_release(msm_context* ctx);
 // throughput mode (bzamd_msm_device_pipelined): the next MSM enqueued on this context leaves its last
 // stages running on the context's own streams; `join_tail` makes `stream` wait for everything pending
 void msm_context_defer_next_tail(msm_context* ctx);

@@ -113,7 +113,9 @@ struct stage_mark {
 // One context per device: the workspace arena, the pinned descriptor ring and the stage timer are
 // shared by every MSM call enqueued on that device.  Calls are asynchronous on a caller stream, so
 // two things keep them from trampling each other's workspace:
-//   * `mu` serialises the host side (arena cursor, staging ring, timer) across caller threads;
+//   * `mu` serialises the host side (arena cursor, staging ring, timer) across caller threads
+//     (recursive: an entry point that enqueues several engine calls around one per-call window
+//     table holds it across all of them, msm_context_hold);
 //   * a call arriving on a DIFFERENT stream than the previous one first makes its stream wait for
 //     everything enqueued on the previous stream (`order_after_previous`) -- calls on one device
 //     therefore execute one after the other whatever streams they come in on; what does overlap
@@ -123,7 +125,7 @@ struct msm_context {
   host_stage_ring descriptors; // pinned copies of the column / task descriptors in flight
   msm_tuning tuning;
   stage_timer timer;
-  std::mutex mu;
+  std::recursive_mutex mu;
   hipEvent_t last_done = nullptr;
   hipStream_t last_stream = nullptr;
   bool has_last = false;
@@ -409,10 +411,10 @@ size_t msm_workspace_bytes(const msm_plan& plan, bool needs_addends, u32 partial
   // what the front writes and the accumulation reads
   size_t front = 0;
   if (needs_addends) {
-    front += device_arena::padded(sizeof(addend) * (plan.max_rows + 1));
+    front += device_arena::padded(sizeof(addend) * (plan.generator_rows + 1));
     if constexpr (C::has_batched_prepare) {
       front += device_arena::padded(sizeof(typename C::batch_fe) *
-                                    batch_prepare_scratch_elements(plan.max_rows));
+                                    batch_prepare_scratch_elements(plan.generator_rows));
     }
   }
   front += device_arena::padded((plan.wide_digits ? sizeof(i32) : sizeof(i16)) * (plan.total_entries + 8));
@@ -461,7 +463,7 @@ void msm_enqueue(msm_context& ctx, u8* d_out, u32 out_stride, bool projective_ou
                  const void* d_api_generators, hipStream_t stream,
                  const window_table* tables = nullptr) {
   if (cols.empty()) return;
-  std::lock_guard<std::mutex> lock(ctx.mu);
+  std::lock_guard<std::recursive_mutex> lock(ctx.mu);
   configure_sort_kernels(ctx);
   ctx.order_after_previous(stream);
   msm_enqueue_locked<C>(ctx, d_out, out_stride, projective_out, cols, d_addends, d_api_generators,
@@ -639,7 +641,8 @@ void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool project
   u64 layout = 0xcbf29ce484222325ull;
   for (u64 v : {static_cast<u64>(plan.total_entries), static_cast<u64>(plan.total_groups),
                 static_cast<u64>(plan.total_buckets), static_cast<u64>(plan.total_segments),
-                static_cast<u64>(plan.max_rows), static_cast<u64>(num_tasks),
+                static_cast<u64>(plan.max_rows), static_cast<u64>(plan.generator_rows),
+                static_cast<u64>(num_tasks),
                 static_cast<u64>(num_cols), static_cast<u64>(b.partial_stride),
                 static_cast<u64>(C::curve_id), static_cast<u64>(sizeof(addend)),
                 static_cast<u64>(d_addends == nullptr),
@@ -705,11 +708,12 @@ void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool project
   [[maybe_unused]] void* prepare_scratch = nullptr; // k_batch_* (curves that normalise per call)
   // carve the arena: the same walk for every batch of a layout, this batch's sets picked out
   {
-    addend* prepared = d_addends == nullptr ? ctx.arena.take<addend>(plan.max_rows + 1) : nullptr;
+    addend* prepared =
+        d_addends == nullptr ? ctx.arena.take<addend>(plan.generator_rows + 1) : nullptr;
     if constexpr (C::has_batched_prepare) {
       if (d_addends == nullptr) {
         prepare_scratch = ctx.arena.take<typename C::batch_fe>(
-            batch_prepare_scratch_elements(plan.max_rows));
+            batch_prepare_scratch_elements(plan.generator_rows));
       }
     }
     void* digits = plan.wide_digits ? static_cast<void*>(ctx.arena.take<i32>(plan.total_entries + 8))
@@ -784,7 +788,7 @@ void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool project
       }
       ctx.timer.timed(timing, 0, ps, [&] {
         launch_prepare_addends_split<C>(const_cast<addend*>(b.addends), d_api_generators,
-                                        plan.max_rows,
+                                        plan.generator_rows,
                                         static_cast<typename C::batch_fe*>(prepare_scratch), ps);
       });
       g_kernel_launches += 2;
@@ -794,7 +798,8 @@ void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool project
       }
     } else {
       ctx.timer.timed(timing, 0, fs, [&] {
-        launch_prepare_addends<C>(const_cast<addend*>(b.addends), d_api_generators, plan.max_rows, fs);
+        launch_prepare_addends<C>(const_cast<addend*>(b.addends), d_api_generators,
+                                  plan.generator_rows, fs);
       });
     }
   }

@@ -34,7 +34,7 @@ inline u32 host_threads(u32 windows) {
   return configured < windows ? configured : windows;
 }
 
-// addends[i] for i < n; cols[].data are HOST pointers here
+// addends[i] for i < max(generator_offset + n); cols[].data are HOST pointers here
 template <class C>
 void msm_host(u8* out, u32 out_stride, bool projective_out, const std::vector<host_column>& cols,
               const typename C::addend* addends) {
@@ -64,7 +64,7 @@ void msm_host(u8* out, u32 out_stride, bool projective_out, const std::vector<ho
           const int d = digits[r * W + w];
           if (d == 0) continue;
           any = true;
-          C::accumulate(buckets[(d < 0 ? -d : d) - 1], addends[r], d < 0);
+          C::accumulate(buckets[(d < 0 ? -d : d) - 1], addends[col.generator_offset + r], d < 0);
         }
         if (!any) return;
         point run = C::identity();

@@ -897,7 +897,7 @@ __global__ void __launch_bounds__(kSortThreads, 8) // <= 64 VGPRs: two workgroup
 }
 
 // Pass 2: counting sort of every group's records by bucket.
-//   sorted[task.entry_base + pos] = row | (digit negative) << 31, grouped by bucket;
+//   sorted[task.entry_base + pos] = (task.row_base + row) | (digit negative) << 31, grouped by bucket;
 //   bucket_end[task.bucket_base + b] = end offset of bucket b in the task's sorted list;
 //   segment_bucket[task.segment_base + pos / 32] = bucket of the entry that starts a segment.
 // One workgroup per (task, group): a group of at most kLocalSortCapacity records
@@ -1040,7 +1040,8 @@ group_sort_block(u32 g, const task_desc& task, u32* __restrict__ sorted,
       }
     }
     lds_barrier();
-    for (u32 i = tid; i < total; i += kGroupSortThreads) out[i] = staging[i];
+    // (row_base + row < 2^31: the add never reaches the sign bit)
+    for (u32 i = tid; i < total; i += kGroupSortThreads) out[i] = staging[i] + task.row_base;
   } else {
     for (u32 base = 0; base < total; base += kLocalSortCapacity) {
       u32 pos[kLocalSortPerThread];
@@ -1059,7 +1060,7 @@ group_sort_block(u32 g, const task_desc& task, u32* __restrict__ sorted,
 #pragma unroll
       for (u32 k = 0; k < kLocalSortPerThread; ++k) {
         if (base + tid + k * kGroupSortThreads < total) {
-          out[pos[k]] = (mine[k] & 0x80000000u) | (mine[k] & row_mask);
+          out[pos[k]] = ((mine[k] & 0x80000000u) | (mine[k] & row_mask)) + task.row_base;
           if (((begin + pos[k]) & seg_mask) == 0) {
             seg[(begin + pos[k]) >> seg_log2] = (g << s) + ((mine[k] >> shift) & in_group);
           }
@@ -1267,7 +1268,7 @@ big_sort_body(u32 worker, u32 workers, u32* __restrict__ sorted, u32* __restrict
         const u32 r = staging[i];
         const u32 b = (r >> shift) & in_group;
         const u32 at = run_base[b] + (i - local_start[b]); // group-relative position
-        out[at] = (r & 0x80000000u) | (r & row_mask);
+        out[at] = ((r & 0x80000000u) | (r & row_mask)) + task.row_base;
         if (((group_begin + at) & seg_mask) == 0) {
           seg[(group_begin + at) >> seg_log2] = (g << s) + b;
         }
@@ -1361,7 +1362,7 @@ __global__ void __launch_bounds__(kGroupSortThreads, 8)
   }
   lds_barrier();
   u32* out = sorted + task.entry_base;
-  for (u32 i = tid; i < total; i += kGroupSortThreads) out[i] = staging[i];
+  for (u32 i = tid; i < total; i += kGroupSortThreads) out[i] = staging[i] + task.row_base;
 }
 
 // Pass 2 with the oversized groups inside the same launch: one more row of the grid

@@ -19,6 +19,8 @@
 #pragma once
 
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <vector>
 
 #include "blitzar_amd/csrc/base/macros.h"
@@ -133,6 +135,10 @@ struct task_desc {
   u64 entry_base;   // first entry of this task in the flat digit / record / sorted-index arrays
   u64 group_base;   // first entry of this task's group tables (num_groups + 1 entries)
   u64 segment_base; // first segment of this task in the flat per-segment arrays
+  // generator of the task's row 0 (the column's generator offset): added to every sorted entry as it
+  // is written, so k_accumulate gathers addends[row_base + row] -- or, merged, table row
+  // w * stride + row_base + row.  row_base + rows < 2^31 (entries are sign | 31-bit row).
+  u32 row_base;
 };
 
 // device-visible column descriptor
@@ -182,6 +188,7 @@ struct msm_plan {
   u64 max_rows = 0;        // longest column
   u64 max_task_rows = 0;   // most (virtual) rows of a task: k_accumulate's grid
   u64 max_recode_rows = 0; // rows k_recode visits per column (merged columns: the table stride)
+  u64 generator_rows = 0;  // addends the launch reads: max over columns of generator_offset + n
   u32 max_task_buckets = 0;
   u32 max_task_slices = 0;
   u32 max_task_groups = 0;
@@ -278,7 +285,20 @@ struct host_column {
   u32 bit_offset;
   u32 bit_width;
   bool is_signed;
+  // row r of the column is paired with generator generator_offset + r of the call's sequence
+  // (bzamd_*_offsets; 0 for every other entry point)
+  u64 generator_offset = 0;
 };
+
+// generators a set of columns reads: max over columns of generator_offset + n (the longest column
+// when every offset is 0)
+inline u64 generator_rows_of(const std::vector<host_column>& cols) {
+  u64 rows = 0;
+  for (const auto& c : cols) {
+    if (c.n != 0 && c.generator_offset + c.n > rows) rows = c.generator_offset + c.n;
+  }
+  return rows;
+}
 
 // one `sxt_sequence_descriptor`: n little-endian integers of nbytes bytes, back to back
 inline host_column byte_column(const u8* data, u64 n, u32 nbytes, bool is_signed) {
@@ -326,7 +346,7 @@ inline partition_geometry choose_partition(u64 n, u32 window_bits,
 inline bool use_window_table(const host_column& hc, const window_table* tables,
                              const msm_tuning& tune, double bucket_cost, double task_cost = 0.0) {
   if (tables == nullptr || tables->windows == 0 || hc.is_signed || hc.n == 0) return false;
-  if (hc.n > tables->stride || 2 * hc.n < tables->stride) return false;
+  if (hc.generator_offset + hc.n > tables->stride || 2 * hc.n < tables->stride) return false;
   const u32 w = ceil_div_u32(hc.bit_width + 1, tables->bits);
   if (w <= 1 || w > tables->windows) return false;
   if (tune.force_window_tables) return true;
@@ -374,7 +394,11 @@ inline call_table_choice choose_call_table(const std::vector<host_column>& cols,
   }
   if (nonempty < (force_bits != 0 ? 1 : kCallTableMinColumns) || max_n == 0) return out;
   if (nonempty < tune.throughput_columns && force_bits == 0) return out;
-  const u64 stride = (max_n + 7) & ~u64{7};
+  // a slice spans every generator the call reads (the union of the columns' windows): shared
+  // windows make it the longest column, disjoint ones (per-column generator offsets) make it long
+  // enough that no column fills half a slice and the model never builds it
+  const u64 union_rows = generator_rows_of(cols);
+  const u64 stride = (union_rows + 7) & ~u64{7};
   // distinct column shapes (a call's columns mostly share one)
   struct shape_count {
     u64 n;
@@ -439,7 +463,7 @@ inline call_table_choice choose_call_table(const std::vector<host_column>& cols,
     if (static_cast<double>(addend_size) * static_cast<double>(stride) * windows > kCallTableMaxBytes) {
       continue;
     }
-    const double build = static_cast<double>(max_n) * (0.8 * c * (windows - 1) + 0.5 * windows) +
+    const double build = static_cast<double>(union_rows) * (0.8 * c * (windows - 1) + 0.5 * windows) +
                          kCallTableLatencyUnits;
     if (total + build < best || (force_bits != 0 && out.shape.windows == 0)) {
       best = total + build;
@@ -536,6 +560,9 @@ inline msm_plan make_msm_plan(const std::vector<host_column>& cols, const msm_tu
     cd.bit_width = hc.bit_width;
     cd.is_signed = hc.is_signed ? 1 : 0;
     cd.first_task = static_cast<u32>(plan.tasks.size());
+    if (hc.n != 0 && hc.generator_offset + hc.n > plan.generator_rows) {
+      plan.generator_rows = hc.generator_offset + hc.n;
+    }
     if (hc.n == 0) {
       cd.window_bits = 1;
       cd.num_windows = 0;
@@ -547,6 +574,12 @@ inline msm_plan make_msm_plan(const std::vector<host_column>& cols, const msm_tu
     const u32 c = sh.c, w = sh.w;
     const u32 buckets = 1u << (c - 1);
     const u64 task_rows = sh.task_rows;
+    // sorted entries hold sign | 31-bit row: the base and the task's rows share the 31 bits
+    // (callers cut longer ranges into passes, api/capi.hip)
+    if (hc.generator_offset + task_rows >= (u64{1} << 31)) {
+      std::fprintf(stderr, "blitzar_amd: generator offset + rows of a task must stay below 2^31\n");
+      std::abort();
+    }
     // A merged task's top slice is not uniform: scalars below 2^252 in 256-bit fields leave a few bits
     // (or only the carry) to the top window, so ALL of that slice's rows land in the lowest bucket
     // group, on top of the group's share of the other slices.  With short slices (per-call tables of a
@@ -579,6 +612,7 @@ inline msm_plan make_msm_plan(const std::vector<host_column>& cols, const msm_tu
       t.entry_base = plan.total_entries;
       t.group_base = plan.total_groups;
       t.segment_base = plan.total_segments;
+      t.row_base = static_cast<u32>(hc.generator_offset);
       plan.total_buckets += buckets;
       // keep every task's entry range 16-byte aligned for both the i16 and the u32 views
       plan.total_entries += (task_rows + 7) & ~7ull;

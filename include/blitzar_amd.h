@@ -220,6 +220,37 @@ void bzamd_msm_device_resident(void* commitments, uint32_t num_sequences,
                                const struct sxt_sequence_descriptor* descriptors,
                                const struct bzamd_generators* gens, void* stream);
 
+/* Per-column generator offsets: independent MSMs over different windows of ONE generator sequence
+ * G in one call,
+ *   commitments[i] = sum_j scalar_ij * G[generator_offsets[i] + j]
+ * (appending rows to tables of different lengths; batched MSMs with non-shared bases laid out back
+ * to back).  generator_offsets == NULL means every offset is 0: the bytes of the corresponding call
+ * without offsets.  A column with generator_offsets[i] + n_i > num_generators aborts, like a bad
+ * descriptor.  Only the generators in [min offset_i, max offset_i + n_i) are uploaded or converted.
+ * Descriptors, encodings and generator layouts as in the calls without offsets. */
+/* HOST operands, blocking, cpu and gpu backends (as sxt_*_compute_pedersen_commitments_with_generators) */
+void bzamd_compute_commitments_with_generator_offsets(unsigned curve_id, void* commitments,
+                                                      uint32_t num_sequences,
+                                                      const struct sxt_sequence_descriptor* descriptors,
+                                                      const void* generators, uint64_t num_generators,
+                                                      const uint64_t* generator_offsets);
+/* built-in ristretto generators (as sxt_curve25519_compute_pedersen_commitments; the sequence has
+ * no end) */
+void bzamd_curve25519_compute_commitments_with_offsets(struct sxt_ristretto255_compressed* commitments,
+                                                       uint32_t num_sequences,
+                                                       const struct sxt_sequence_descriptor* descriptors,
+                                                       const uint64_t* generator_offsets);
+/* DEVICE operands (as bzamd_msm_device), generator_offsets on the HOST, async */
+void bzamd_msm_device_offsets(unsigned curve_id, void* commitments, uint32_t num_sequences,
+                              const struct sxt_sequence_descriptor* descriptors,
+                              const void* generators, uint64_t num_generators,
+                              const uint64_t* generator_offsets, void* stream);
+/* resident set (as bzamd_msm_device_resident; num_generators = the set's), async */
+void bzamd_msm_device_resident_offsets(void* commitments, uint32_t num_sequences,
+                                       const struct sxt_sequence_descriptor* descriptors,
+                                       const struct bzamd_generators* gens,
+                                       const uint64_t* generator_offsets, void* stream);
+
 /* DEVICE built-in ristretto generators g_first .. g_first+n-1 as sxt_ristretto255 (async) */
 void bzamd_ristretto255_generators_device(struct sxt_ristretto255* generators, uint64_t first,
                                           uint64_t n, void* stream);
