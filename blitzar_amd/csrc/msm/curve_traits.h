@@ -46,6 +46,11 @@ struct ed25519_msm {
   // (measured on MI355X at config 2: 2 / 3 / 4 waves per SIMD -> 0.862 / 0.860 / 1.13 ms, the last
   // one spills: the kernel is issue-bound, not latency-bound)
   static constexpr int accumulate_waves_per_simd = 3;
+  // waves per SIMD that k_accumulate's launch bound names: a scheduling bound only.  Under a bound
+  // of two waves the caller-generators loop keeps its 140 VGPRs -- still three waves resident, which
+  // is what accumulate_wave_slots counts -- but loses a third of its s_nop padding
+  // (blitzar_amd/build.py); the Z = 1 loop keeps the bound of its occupancy
+  static constexpr int accumulate_launch_waves = 2;
   static constexpr bool has_batched_prepare = false;
   static constexpr double call_table_entry_cost = 1.0;
 
@@ -81,18 +86,6 @@ struct ed25519_msm {
     acc = ed29::add_cached_presigned(acc, q, negate);
   }
   // identity + (+-q) of a segment's first entry: loaded, not added (k_accumulate)
-  // the addition in two halves with no operand live between them (k_accumulate, BZ_ACCUMULATE_DIRECT=2)
-  static constexpr bool has_split_add = true;
-  using completed = ed29::ed29_completed;
-  BZ_HD static completed add_front(const point& acc, const operand& q, bool negate) {
-    completed m = ed29::add_cached_presigned_front(acc, q, negate);
-    f29::pin(m.ex);
-    f29::pin(m.ey);
-    f29::pin(m.ez);
-    f29::pin(m.et);
-    return m;
-  }
-  BZ_HD static point add_back(const completed& m) { return ed29::add_cached_back(m); }
   static constexpr bool first_pinned = true; // (see k_accumulate)
   BZ_HD static point first_gathered(const operand& q, bool negate) {
     return ed29::from_cached_presigned(q, negate);
@@ -227,10 +220,10 @@ struct ed25519_msm {
 // bzamd_generators, handles): Z = 1 addends of 128 bytes, 7 instead of 8 products per addition
 struct ed25519_niels_msm : ed25519_msm {
   using addend = ed29_niels;
+  static constexpr int accumulate_launch_waves = accumulate_waves_per_simd;
   BZ_HD static void accumulate(point& acc, const addend& q, bool negate) {
     acc = ed29::add_niels(acc, q, negate);
   }
-  static constexpr bool has_split_add = false;
   BZ_HD static point first(const addend& q, bool negate) { return ed29::from_niels(q, negate); }
   static constexpr bool has_signed_gather = false; // 36-byte limb pieces: no aligned exchange
   // an accumulated entry against Z = 1 addends relative to the per-call (Y+X, Y-X, Z, 2dT) form
@@ -291,30 +284,21 @@ template <class G29, unsigned CurveId> struct sw_msm_base {
   using api_affine = sw_api_affine<N64>;
   static constexpr size_t api_generator_size = sizeof(api_affine);
   static constexpr size_t projective_size = sizeof(api_projective);
-#ifndef BZ_ACC_WAVES_SW9
-#define BZ_ACC_WAVES_SW9 3
-#endif
-  static constexpr int accumulate_waves_per_simd = G29::N <= 9 ? BZ_ACC_WAVES_SW9 : 2;
+  static constexpr int accumulate_waves_per_simd = G29::N <= 9 ? 3 : 2;
+  static constexpr int accumulate_launch_waves = accumulate_waves_per_simd; // (see ed25519_msm)
   // k_accumulate's additions use the pinned product-scanning field products (field/mont29.h) on the
   // 9-limb curves: config 4 accumulate 348.3 -> 338.8 ms, config 5 138.1 -> 135.1 (A/B on one box,
   // profiles/round2_ab_pinned_products.log).  With 14 limbs the quotient digits and the single
   // chain spill (bls12-381: 11.3 -> 170 ms); there the operand-scanning product keeps its N
   // accumulators and only pins their order (msm_bls12_381.hip).
-#ifndef BZ_SW_ACCUMULATE_PINNED
-#define BZ_SW_ACCUMULATE_PINNED 1
-#endif
-  static constexpr bool accumulate_pinned = BZ_SW_ACCUMULATE_PINNED != 0 && G29::N <= 9;
+  static constexpr bool accumulate_pinned = G29::N <= 9;
   static constexpr bool has_batched_prepare = false;
   static constexpr bool has_signed_gather = false;
   static constexpr bool has_wave_encode = false;
   // k_reduce's lane weights as a suffix scan over the lanes (8 additions per lane instead of a
   // 15-bit double-and-add); the one multiple left per workgroup -- the block's first bucket index
-  // times the block's plain sum -- by a whole wavefront on the lane-spread form (curve/sw_wave.h).
-  // BZ_SW_REDUCE_SCAN=0: the per-lane double-and-add of rounds 1-3.
-#ifndef BZ_SW_REDUCE_SCAN
-#define BZ_SW_REDUCE_SCAN 1
-#endif
-  static constexpr bool has_wave_add_multiple = BZ_SW_REDUCE_SCAN != 0;
+  // times the block's plain sum -- by a whole wavefront on the lane-spread form (curve/sw_wave.h)
+  static constexpr bool has_wave_add_multiple = true;
   // only for launches of few columns (engine.h; see k_reduce): many columns keep the per-lane form
   static constexpr bool reduce_scan_few_columns_only = true;
 #if defined(__HIPCC__)
@@ -332,12 +316,7 @@ template <class G29, unsigned CurveId> struct sw_msm_base {
   }
 #endif
   // k_horner's dependent chain on one wavefront: the point spread over the wavefront, limb j of a
-  // coordinate in lane j of a DPP row, four field products at once (curve/sw_wave.h).
-  // BZ_SW_WAVE_HORNER=0: the form of rounds 2-3 -- doublings split over the lanes of each DPP quad
-  // (curve/sw29_coop.h), the one addition per window computed redundantly by every lane.
-#ifndef BZ_SW_WAVE_HORNER
-#define BZ_SW_WAVE_HORNER 1
-#endif
+  // coordinate in lane j of a DPP row, four field products at once (curve/sw_wave.h)
   static constexpr bool has_wave_horner = true;
 #if defined(__HIPCC__)
   // out[w * stride] = 2^(bits w) g for w < windows by one wavefront (see ed25519_msm::wave_chain)
@@ -356,22 +335,8 @@ template <class G29, unsigned CurveId> struct sw_msm_base {
   }
   __device__ static point wave_horner(point acc, bool have_acc, point* window_sums,
                                       u32 stride, u32 num_windows, u32 window_bits) {
-#if BZ_SW_WAVE_HORNER
     return sww::wave<G29>::horner(sww::wave_scratch(), acc, have_acc, window_sums, stride,
                                   num_windows, window_bits);
-#else
-    const u32 role = threadIdx.x & 3;
-    u32 i = num_windows;
-    if (!have_acc) {
-      acc = window_sums[(num_windows - 1) * stride];
-      i = num_windows - 1;
-    }
-    while (i-- > 0) {
-      for (u32 k = 0; k < window_bits; ++k) acc = sw29_coop::dbl_coop4<G29>(acc, role);
-      acc = G29::add(acc, window_sums[i * stride]);
-    }
-    return acc;
-#endif
   }
 #endif
 
@@ -443,7 +408,6 @@ template <class G29, unsigned CurveId> struct sw_msm_base {
   }
   // identity + (+-q) of a segment's first entry: the affine point itself (k_accumulate)
   static constexpr bool first_pinned = false;
-  static constexpr bool has_split_add = false;
   BZ_HD static point first(const operand& q, bool negate) {
     if (q.nonzero == 0) return G29::identity();
     return G29::lift_acc(q.a, negate);

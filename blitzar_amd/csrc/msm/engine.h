@@ -165,14 +165,6 @@ struct msm_context {
   // fork / join pair costs ~25 us of stream bubbles).
   hipStream_t tail = nullptr, tail2 = nullptr; // k_reduce / k_horner of a pipelined batch
   stage_mark acc_done[4], reduce_done[4], horner_done[4];
-  // `pre_horner[k]`: recorded on the k_horner stream behind its wait for reduce(k) and in front of
-  // horner(k) -- that stream runs in order, so the mark fires when horner(k - 1) AND reduce(k) are
-  // done.  The caller's stream waits for this ONE mark per batch (end of batch k: pre_horner[k - 1])
-  // instead of for horner_done[k - 2] there and for reduce_done[k - 1] in front of the next batch's
-  // front and again in front of its accumulation: every cross-stream wait is a barrier packet that
-  // costs the queue 8-12 us (round 6 timeline: 24 us between k_accumulate and the next front, 13 us
-  // in front of k_accumulate -- profiles/round6_timeline_sequence.txt).
-  stage_mark pre_horner[4];
   u64 reduce_joined = 0; // `reduce_joined_on` has waited for the reduce of every batch below this
   hipStream_t reduce_joined_on = nullptr;
   // Per-call window tables (plan.h, choose_call_table; built by curve_tu.h, build_call_table): the
@@ -190,15 +182,6 @@ struct msm_context {
   bool call_tables = true;
   bool table_overlap = true;
   bool wave_chain = true; // BLITZAR_AMD_CALL_TABLE_WAVE_CHAIN=0: a lane per generator whatever the set's size
-  // curve25519, BLITZAR_AMD_NORMALISE_CALLER=1: caller generators are normalised to Z = 1 in every
-  // call (kernels.h, k_batch_*: three launches, no workgroup waits for an inversion) and the
-  // accumulation runs the 7-product loop of resident sets.  OFF by default, measured on MI355X at
-  // config 2 (profiles/round6_ab_normalise_caller.log): k_accumulate 0.618 -> 0.573 ms, but the
-  // normalisation takes 0.200 ms against the 0.066 of the plain conversion -- a lone call 1.17 ->
-  // 1.26 ms, a step in sequence 0.978 -> 1.054 -- and on the side stream beside recode + sort
-  // (BLITZAR_AMD_CALL_TABLE_OVERLAP) every memory-bound kernel of the front takes 2.5-4x as long
-  // (recode 0.018 -> 0.07, sort 0.11 -> 0.27; step 1.16).
-  bool normalise_caller = false;
   u32 force_call_table_bits = 0;
   u64 call_tables_built = 0; // (tests: bzamd_set_call_tables returns it)
   const void* call_table_rows = nullptr; // slice 0 of the table built last
@@ -270,33 +253,11 @@ struct msm_context {
   // batch k reused, so it is long done): a pipelined result is complete on the stream once two
   // further calls have been enqueued, or after a flush.  (Waiting for the previous batch here
   // would put its k_horner in front of whatever the caller enqueues next.)
-  // BLITZAR_AMD_MERGED_WAITS=1: one wait per batch (pre_horner) instead of three.  OFF: measured on
-  // one MI355X box, 4 x 300 steps each (profiles/round6_ab_merged_waits.log): the gaps shrink (24 ->
-  // 17 us behind k_accumulate, 13 -> 6.5 us in front of it) and the step does not -- 0.9701 against
-  // 0.9729 ms with the single wait: k_reduce and the sort stretch by what the gaps gave up.  The step
-  // in throughput mode is bound by the work of its stages, not by the packets between them.
-  bool merged_waits = false;
-  // BLITZAR_AMD_ACC_LDS_PAD=<bytes>: dynamic LDS requested by k_accumulate (which uses none), i.e. a cap
-  // on its workgroups per compute unit -- 55000 leaves two of the three wavefronts per SIMD its
-  // registers allow, and the third slot's registers to whatever runs beside it (the tails of the
-  // previous calls in throughput mode)
-  u32 acc_lds_pad = 0;
   void join_two_back(hipStream_t stream, u64 k) {
-    if (!merged_waits) {
-      if (k >= 2 && (joined < k - 1 || stream != joined_on)) {
-        horner_done[(k - 2) & 3].wait(stream);
-        joined = k - 1;
-        joined_on = stream;
-      }
-      return;
-    }
-    if (k >= 1 && (joined < k - 1 || reduce_joined < k || stream != joined_on ||
-                   stream != reduce_joined_on)) {
-      pre_horner[(k - 1) & 3].wait(stream); // horner(k - 2) and reduce(k - 1)
+    if (k >= 2 && (joined < k - 1 || stream != joined_on)) {
+      horner_done[(k - 2) & 3].wait(stream);
       joined = k - 1;
       joined_on = stream;
-      reduce_joined = k;
-      reduce_joined_on = stream;
     }
   }
   // has `stream` already waited for the reduce of batch `batch`?
@@ -335,7 +296,6 @@ struct msm_context {
       acc_done[i].destroy();
       reduce_done[i].destroy();
       horner_done[i].destroy();
-      pre_horner[i].destroy();
     }
     table_fork.destroy();
     table_ready.destroy();
@@ -410,13 +370,7 @@ size_t msm_workspace_bytes(const msm_plan& plan, bool needs_addends, u32 partial
   // (the descriptors live in a block of their own: msm_context::descriptor_block)
   // what the front writes and the accumulation reads
   size_t front = 0;
-  if (needs_addends) {
-    front += device_arena::padded(sizeof(addend) * (plan.generator_rows + 1));
-    if constexpr (C::has_batched_prepare) {
-      front += device_arena::padded(sizeof(typename C::batch_fe) *
-                                    batch_prepare_scratch_elements(plan.generator_rows));
-    }
-  }
+  if (needs_addends) front += device_arena::padded(sizeof(addend) * (plan.generator_rows + 1));
   front += device_arena::padded((plan.wide_digits ? sizeof(i32) : sizeof(i16)) * (plan.total_entries + 8));
   front += 2 * device_arena::padded(sizeof(u32) * (plan.total_entries + 8));
   front += 2 * device_arena::padded(sizeof(u32) * (plan.total_groups + 1));
@@ -483,6 +437,11 @@ void msm_enqueue_locked(msm_context& ctx, u8* d_out, u32 out_stride, bool projec
   pipe_mode mode;
   mode.piped = ctx.defer_tail && ctx.overlap_tails && nonempty_columns < ctx.tuning.defer_max_columns;
   ctx.defer_tail = false;
+  // a curve whose addends need a normalisation (the Z = 1 form of curve25519) runs against resident
+  // sets only: its addends are never converted inside a call
+  if constexpr (C::has_batched_prepare) {
+    BZ_RELEASE_ASSERT(d_addends != nullptr, "Z = 1 addends come from a resident generator set");
+  }
   msm_tuning tune = ctx.tuning;
   tune.in_sequence = mode.piped;
   if (force_tables) tune.force_window_tables = true;
@@ -696,7 +655,6 @@ void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool project
       // keeps its place in the sequence: every mark of the slot points behind this launch
       ctx.acc_done[k & 3].record(hs);
       ctx.reduce_done[k & 3].record(hs);
-      if (ctx.merged_waits) ctx.pre_horner[k & 3].record(hs);
       ctx.horner_done[k & 3].record(hs);
       ctx.pipe_layout = layout;
       ctx.seq = k + 1;
@@ -705,17 +663,10 @@ void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool project
     return;
   }
   const bool timing = ctx.timer.recording();
-  [[maybe_unused]] void* prepare_scratch = nullptr; // k_batch_* (curves that normalise per call)
   // carve the arena: the same walk for every batch of a layout, this batch's sets picked out
   {
     addend* prepared =
         d_addends == nullptr ? ctx.arena.take<addend>(plan.generator_rows + 1) : nullptr;
-    if constexpr (C::has_batched_prepare) {
-      if (d_addends == nullptr) {
-        prepare_scratch = ctx.arena.take<typename C::batch_fe>(
-            batch_prepare_scratch_elements(plan.generator_rows));
-      }
-    }
     void* digits = plan.wide_digits ? static_cast<void*>(ctx.arena.take<i32>(plan.total_entries + 8))
                                     : static_cast<void*>(ctx.arena.take<i16>(plan.total_entries + 8));
     u32* records = ctx.arena.take<u32>(plan.total_entries + 8);
@@ -775,33 +726,10 @@ void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool project
   // the one HBM-saturating kernel of the front inside the LDS-bound one -- was built and measured in
   // round 3: sort + conversion 0.171 -> 0.183 ms, profiles/round3_ab_front_fusion.log; removed.)
   if (d_addends == nullptr) {
-    if constexpr (C::has_batched_prepare) {
-      // Z = 1 normalisation (kernels.h, k_batch_*): only k_accumulate reads the addends, so the three
-      // launches -- the middle one a latency chain on ONE compute unit -- run on the side stream
-      // beside the recoding and the sort, like the build of a per-call window table
-      hipStream_t ps = fs;
-      if (ctx.table_overlap) {
-        ctx.make_side_stream();
-        ctx.table_fork.record(fs);
-        ctx.table_fork.wait(ctx.side);
-        ps = ctx.side;
-      }
-      ctx.timer.timed(timing, 0, ps, [&] {
-        launch_prepare_addends_split<C>(const_cast<addend*>(b.addends), d_api_generators,
-                                        plan.generator_rows,
-                                        static_cast<typename C::batch_fe*>(prepare_scratch), ps);
-      });
-      g_kernel_launches += 2;
-      if (ctx.table_overlap) {
-        ctx.table_ready.record(ps);
-        ctx.table_pending = true;
-      }
-    } else {
-      ctx.timer.timed(timing, 0, fs, [&] {
-        launch_prepare_addends<C>(const_cast<addend*>(b.addends), d_api_generators,
-                                  plan.generator_rows, fs);
-      });
-    }
+    ctx.timer.timed(timing, 0, fs, [&] {
+      launch_prepare_addends<C>(const_cast<addend*>(b.addends), d_api_generators,
+                                plan.generator_rows, fs);
+    });
   }
   // group cursors, arrival tickets, the workers' barrier, big_tasks[0]: cleared by the recode kernel
   const u64 zero_words = plan.total_groups + 1 + num_tasks + 2;
@@ -912,8 +840,8 @@ void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool project
     ctx.table_pending = false;
   }
   ctx.timer.timed(timing, 3, as, [&] {
-    hipLaunchKernelGGL((k_accumulate<C>), dim3(seg_blocks, num_tasks), dim3(kAccumulateThreads),
-                       ctx.acc_lds_pad, as, b.bucket_sums, b.heads, b.bucket_end, b.segment_bucket, b.sorted,
+    hipLaunchKernelGGL((k_accumulate<C>), dim3(seg_blocks, num_tasks), dim3(kAccumulateThreads), 0,
+                       as, b.bucket_sums, b.heads, b.bucket_end, b.segment_bucket, b.sorted,
                        b.addends, b.tasks);
   });
   if (mode.piped) ctx.acc_done[k & 3].record(as);
@@ -957,10 +885,7 @@ void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool project
   if (mode.piped) ctx.reduce_done[k & 3].record(rs);
 
   // ---- horner: whole columns in one launch (the range covers every window, first and last)
-  if (mode.piped) {
-    ctx.reduce_done[k & 3].wait(hs);
-    if (ctx.merged_waits) ctx.pre_horner[k & 3].record(hs);
-  }
+  if (mode.piped) ctx.reduce_done[k & 3].wait(hs);
   ctx.timer.timed(timing, 5, hs, [&] {
     // (hundreds of columns: one-wavefront blocks, kernels.h)
     if (num_cols >= 64 && plan.max_windows <= 64) {

@@ -14,7 +14,7 @@
 //                      segment -> bucket map
 //                      (together a two-pass radix sort by bucket; reference K1/K2:
 //                       bucket_method2/multiproduct_table_kernel.h:32-93, multiproduct_table.cc:74-82)
-//   k_accumulate       one lane per 32 consecutive *sorted entries* (not per bucket): gather
+//   k_accumulate       one lane per 8..128 consecutive *sorted entries* (not per bucket): gather
 //                      addends, mixed-add, flush at bucket boundaries; a bucket that straddles
 //                      lanes leaves "head" partials that k_reduce folds in
 //                      (reference K3 bucket_method2/sum.h:41-72, K5 bucket_method/
@@ -49,14 +49,6 @@ constexpr u32 kReduceHeavyHeads = 16;
 constexpr u32 kReduceMaxHeavy = 8;
 constexpr u32 kAccumulateThreads = 256;
 constexpr u32 kCombineThreads = 256;
-#ifndef BZ_FRONT_PRIO
-#define BZ_FRONT_PRIO 0
-#endif
-__device__ __forceinline__ void front_priority() {
-#if BZ_FRONT_PRIO != 0
-  __builtin_amdgcn_s_setprio(BZ_FRONT_PRIO);
-#endif
-}
 
 //--------------------------------------------------------------------------------------------------
 // k_prepare_addends
@@ -86,7 +78,6 @@ template <class C>
 __global__ void __launch_bounds__(256)
     k_prepare_addends_staged(typename C::addend* __restrict__ addends,
                              const void* __restrict__ api_generators, u64 n) {
-  front_priority();
   using addend = typename C::addend;
   constexpr u32 G = static_cast<u32>(C::api_generator_size);
   constexpr u32 A = static_cast<u32>(sizeof(addend));
@@ -138,9 +129,6 @@ template <u32 N, class F> __device__ __forceinline__ void static_for(F&& f) {
     (f(std::integral_constant<u32, J>{}), ...);
   }(std::make_integer_sequence<u32, N>{});
 }
-#ifndef BZ_BATCH_PREPARE_WAVES
-#define BZ_BATCH_PREPARE_WAVES 1
-#endif
 // Montgomery's trick across a workgroup of T lanes (T a power of two): `tree` has 2 T entries in
 // heap order (root 1, leaf T + lane).  tree_products: leaves -> products of every subtree, root in
 // tree[1].  tree_inverses: with tree[1] replaced by the inverse of the root, every node becomes
@@ -169,7 +157,7 @@ __device__ __forceinline__ void tree_inverses(typename C::batch_fe* tree, u32 ti
 }
 
 template <class C>
-__global__ void __launch_bounds__(kBatchPrepareThreads, BZ_BATCH_PREPARE_WAVES)
+__global__ void __launch_bounds__(kBatchPrepareThreads, 1)
     k_prepare_addends_batched(typename C::addend* __restrict__ addends,
                               const void* __restrict__ api_generators, u64 n) {
   using fe = typename C::batch_fe;
@@ -207,146 +195,6 @@ __global__ void __launch_bounds__(kBatchPrepareThreads, BZ_BATCH_PREPARE_WAVES)
   });
 }
 
-// The same normalisation without a workgroup waiting for its own inversion: k_prepare_addends_batched
-// has every workgroup of the launch sit through a ~50 us exponentiation at the same time (all but one
-// of its wavefronts idle), which is what made per-call normalisation lose in round 2.  Split in
-// three launches, the machine-wide part has no latency chain in it and the chain runs ONCE, on one
-// compute unit, beside whatever else the call has to do (recoding, the sort):
-//   k_batch_products   every workgroup multiplies its 1024 Z's up (lane prefixes + the LDS tree) and
-//                      writes ONE field element, the product of them all;
-//   k_batch_invert     one workgroup per 1024 of those products: the same trick one level up, one
-//                      wave-cooperative inversion per workgroup (2^20 generators: ONE workgroup);
-//   k_batch_finish     every workgroup rebuilds its prefixes and tree (3 + 1 products per generator:
-//                      cheaper than keeping 40 KiB of them per workgroup between the launches), takes
-//                      the inverse of its product from k_batch_invert, walks it down the tree and
-//                      the prefixes, and writes the Z = 1 addends.
-template <class C>
-__device__ __forceinline__ void batch_prefixes(typename C::batch_fe (&z)[kBatchPreparePoints],
-                                               typename C::batch_fe (&prefix)[kBatchPreparePoints],
-                                               const void* __restrict__ api_generators, u64 base,
-                                               u64 n, u32 tid) {
-  static_for<kBatchPreparePoints>([&](auto jc) {
-    constexpr u32 j = decltype(jc)::value;
-    const u64 i = base + static_cast<u64>(j) * kBatchPrepareThreads + tid;
-    z[j] = i < n ? C::batch_load_z(api_generators, i) : C::batch_one();
-    if constexpr (j == 0) {
-      prefix[0] = z[0];
-    } else {
-      prefix[j] = C::batch_mul(prefix[j - 1], z[j]);
-    }
-  });
-}
-
-template <class C>
-__global__ void __launch_bounds__(kBatchPrepareThreads)
-    k_batch_products(typename C::batch_fe* __restrict__ block_products,
-                     const void* __restrict__ api_generators, u64 n) {
-  using fe = typename C::batch_fe;
-  front_priority();
-  __shared__ fe tree[2 * kBatchPrepareThreads];
-  const u32 tid = threadIdx.x;
-  const u64 base = static_cast<u64>(blockIdx.x) * kBatchPrepareThreads * kBatchPreparePoints;
-  fe z[kBatchPreparePoints], prefix[kBatchPreparePoints];
-  batch_prefixes<C>(z, prefix, api_generators, base, n, tid);
-  tree[kBatchPrepareThreads + tid] = prefix[kBatchPreparePoints - 1];
-  tree_products<C, kBatchPrepareThreads>(tree, tid);
-  if (tid == 0) block_products[blockIdx.x] = tree[1];
-}
-
-// block_inverses[b] = 1 / block_products[b], 1024 per workgroup with one shared inversion
-template <class C>
-__global__ void __launch_bounds__(kBatchPrepareThreads)
-    k_batch_invert(typename C::batch_fe* __restrict__ block_inverses,
-                   const typename C::batch_fe* __restrict__ block_products, u32 num_blocks) {
-  using fe = typename C::batch_fe;
-  __builtin_amdgcn_s_setprio(3); // a latency chain on one compute unit, beside the call's front
-  __shared__ fe tree[2 * kBatchPrepareThreads];
-  const u32 tid = threadIdx.x;
-  const u32 base = blockIdx.x * kBatchPrepareThreads * kBatchPreparePoints;
-  fe z[kBatchPreparePoints], prefix[kBatchPreparePoints];
-  static_for<kBatchPreparePoints>([&](auto jc) {
-    constexpr u32 j = decltype(jc)::value;
-    const u32 i = base + j * kBatchPrepareThreads + tid;
-    z[j] = i < num_blocks ? block_products[i] : C::batch_one();
-    if constexpr (j == 0) {
-      prefix[0] = z[0];
-    } else {
-      prefix[j] = C::batch_mul(prefix[j - 1], z[j]);
-    }
-  });
-  tree[kBatchPrepareThreads + tid] = prefix[kBatchPreparePoints - 1];
-  tree_products<C, kBatchPrepareThreads>(tree, tid);
-  if (tid < 64) {
-    const fe inv = C::batch_wave_invert(tree[1]);
-    if (tid == 0) tree[1] = inv;
-  }
-  tree_inverses<C, kBatchPrepareThreads>(tree, tid);
-  fe inv = tree[kBatchPrepareThreads + tid];
-  static_for<kBatchPreparePoints>([&](auto jc) {
-    constexpr u32 j = kBatchPreparePoints - 1 - decltype(jc)::value;
-    fe zinv = inv;
-    if constexpr (j != 0) {
-      zinv = C::batch_mul(inv, prefix[j - 1]);
-      inv = C::batch_mul(inv, z[j]);
-    }
-    const u32 i = base + j * kBatchPrepareThreads + tid;
-    if (i < num_blocks) block_inverses[i] = zinv;
-  });
-}
-
-template <class C>
-__global__ void __launch_bounds__(kBatchPrepareThreads)
-    k_batch_finish(typename C::addend* __restrict__ addends,
-                   const typename C::batch_fe* __restrict__ block_inverses,
-                   const void* __restrict__ api_generators, u64 n) {
-  using fe = typename C::batch_fe;
-  front_priority();
-  __shared__ fe tree[2 * kBatchPrepareThreads];
-  const u32 tid = threadIdx.x;
-  const u64 base = static_cast<u64>(blockIdx.x) * kBatchPrepareThreads * kBatchPreparePoints;
-  fe z[kBatchPreparePoints], prefix[kBatchPreparePoints];
-  batch_prefixes<C>(z, prefix, api_generators, base, n, tid);
-  tree[kBatchPrepareThreads + tid] = prefix[kBatchPreparePoints - 1];
-  tree_products<C, kBatchPrepareThreads>(tree, tid);
-  if (tid == 0) tree[1] = block_inverses[blockIdx.x];
-  tree_inverses<C, kBatchPrepareThreads>(tree, tid);
-  fe inv = tree[kBatchPrepareThreads + tid];
-  static_for<kBatchPreparePoints>([&](auto jc) {
-    constexpr u32 j = kBatchPreparePoints - 1 - decltype(jc)::value;
-    fe zinv = inv;
-    if constexpr (j != 0) {
-      zinv = C::batch_mul(inv, prefix[j - 1]);
-      inv = C::batch_mul(inv, z[j]);
-    }
-    const u64 i = base + static_cast<u64>(j) * kBatchPrepareThreads + tid;
-    if (i < n) addends[i] = C::batch_make_addend(api_generators, i, zinv);
-  });
-}
-
-// field elements of scratch the three launches need for n generators (products | inverses)
-inline size_t batch_prepare_scratch_elements(u64 n) {
-  const u64 per_block = static_cast<u64>(kBatchPrepareThreads) * kBatchPreparePoints;
-  return 2 * static_cast<size_t>((n + per_block - 1) / per_block) + 2;
-}
-template <class C>
-void launch_prepare_addends_split(typename C::addend* d_addends, const void* d_api_generators, u64 n,
-                                  typename C::batch_fe* d_scratch, hipStream_t stream) {
-  if (n == 0) return;
-  const u64 per_block = static_cast<u64>(kBatchPrepareThreads) * kBatchPreparePoints;
-  const u32 blocks = ceil_div_u32(n, per_block);
-  typename C::batch_fe* products = d_scratch;
-  typename C::batch_fe* inverses = d_scratch + blocks + 1;
-  hipLaunchKernelGGL((k_batch_products<C>), dim3(blocks), dim3(kBatchPrepareThreads), 0, stream,
-                     products, d_api_generators, n);
-  hipLaunchKernelGGL((k_batch_invert<C>), dim3(ceil_div_u32(blocks, per_block)),
-                     dim3(kBatchPrepareThreads), 0, stream, inverses, products, blocks);
-  hipLaunchKernelGGL((k_batch_finish<C>), dim3(blocks), dim3(kBatchPrepareThreads), 0, stream,
-                     d_addends, inverses, d_api_generators, n);
-}
-
-#ifndef BZ_PREPARE_STAGED
-#define BZ_PREPARE_STAGED 1
-#endif
 // C-ABI generators -> addends, by the curve's cheapest route
 template <class C>
 void launch_prepare_addends(typename C::addend* d_addends, const void* d_api_generators, u64 n,
@@ -357,7 +205,7 @@ void launch_prepare_addends(typename C::addend* d_addends, const void* d_api_gen
     hipLaunchKernelGGL((k_prepare_addends_batched<C>), dim3(ceil_div_u32(n, per_block)),
                        dim3(kBatchPrepareThreads), 0, stream, d_addends, d_api_generators, n);
   } else if ((reinterpret_cast<uintptr_t>(d_api_generators) & 15) == 0 &&
-             (reinterpret_cast<uintptr_t>(d_addends) & 15) == 0 && BZ_PREPARE_STAGED != 0) {
+             (reinterpret_cast<uintptr_t>(d_addends) & 15) == 0) {
     hipLaunchKernelGGL((k_prepare_addends_staged<C>), dim3(ceil_div_u32(n, 256)), dim3(256), 0,
                        stream, d_addends, d_api_generators, n);
   } else {
@@ -383,7 +231,6 @@ __global__ void __launch_bounds__(256)
     k_recode(D* __restrict__ digits, const column_desc* __restrict__ columns,
              const task_desc* __restrict__ tasks, u32 num_columns, u32 num_chunks,
              u32* __restrict__ zero, u64 zero_words) {
-  front_priority();
   // the group cursors of the sort start at zero: cleared here, by the first kernel of the call,
   // instead of by a memset (two fill kernels and two stream bubbles per call)
   for (u64 i = static_cast<u64>(blockIdx.x) * blockDim.x + threadIdx.x; i < zero_words;
@@ -437,7 +284,6 @@ __global__ void __launch_bounds__(256)
 static __global__ void __launch_bounds__(256)
     k_recode_rows32_c16(i16* __restrict__ digits, const column_desc* __restrict__ columns,
                         const task_desc* __restrict__ tasks, u32* __restrict__ zero, u64 zero_words) {
-  front_priority();
   const u64 threads = static_cast<u64>(gridDim.x) * gridDim.y * blockDim.x;
   for (u64 i = (static_cast<u64>(blockIdx.y) * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
        i < zero_words; i += threads) {
@@ -679,7 +525,6 @@ __global__ void __launch_bounds__(kSortThreads, 8) // <= 64 VGPRs: two workgroup
                  u32* __restrict__ arrivals, u32* __restrict__ group_start,
                  u32* __restrict__ group_chunk, u32* __restrict__ bucket_count,
                  u32* __restrict__ bucket_fill, u32 stream_limit) {
-  front_priority();
   extern __shared__ __attribute__((aligned(16))) u32 lds[];
   __shared__ u32 wave_sums[kSortThreads / 64];
   __shared__ u32 wave_chunks[kSortThreads / 64];
@@ -750,7 +595,6 @@ template <bool Staged, class D>
 __global__ void __launch_bounds__(kSortThreads, 8) // <= 64 VGPRs: two workgroups per CU
     k_group_scatter(u32* __restrict__ records, u32* __restrict__ group_cursor,
                     const D* __restrict__ digits, const task_desc* __restrict__ tasks) {
-  front_priority();
   constexpr u32 V = kDigitsPerVector<D>;                   // digits per 16-byte vector: 8 or 4
   constexpr u32 H = kStagedSliceRows / (V * kSortThreads); // vectors a thread holds: 2 or 4
   static_assert(H * V * kSortThreads == kStagedSliceRows);
@@ -899,7 +743,8 @@ __global__ void __launch_bounds__(kSortThreads, 8) // <= 64 VGPRs: two workgroup
 // Pass 2: counting sort of every group's records by bucket.
 //   sorted[task.entry_base + pos] = (task.row_base + row) | (digit negative) << 31, grouped by bucket;
 //   bucket_end[task.bucket_base + b] = end offset of bucket b in the task's sorted list;
-//   segment_bucket[task.segment_base + pos / 32] = bucket of the entry that starts a segment.
+//   segment_bucket[task.segment_base + (pos >> task.segment_log2)] = bucket of the entry that starts a
+//   segment.
 // One workgroup per (task, group): a group of at most kLocalSortCapacity records
 // (nearly every group, on uniform digits) is held in registers, count -> scan -> rank run in LDS, the
 // group's piece of the sorted list is assembled in LDS and written out in order (coalesced).
@@ -1289,7 +1134,6 @@ __global__ void __launch_bounds__(kGroupSortThreads, 8)
     k_task_sort(u32* __restrict__ sorted, u32* __restrict__ segment_bucket,
                 u32* __restrict__ bucket_end, const D* __restrict__ digits,
                 const task_desc* __restrict__ tasks) {
-  front_priority();
   __shared__ sort_lds lds;
   u32* cursor = lds.cursor;
   u32* staging = lds.staging;
@@ -1383,7 +1227,6 @@ static __global__ void __launch_bounds__(kGroupSortThreads, 8) // <= 64 VGPRs: f
                      u32* __restrict__ bucket_count, u32* __restrict__ bucket_fill,
                      const u32* __restrict__ big_tasks, u32* __restrict__ big_barrier,
                      u32 max_workers) {
-  front_priority();
   __shared__ sort_lds lds;
   if (blockIdx.y < num_tasks) {
     const task_desc task = tasks[blockIdx.y];
@@ -1418,7 +1261,7 @@ static __global__ void __launch_bounds__(kGroupSortThreads, 8) // <= 64 VGPRs: f
 //--------------------------------------------------------------------------------------------------
 // k_accumulate
 //--------------------------------------------------------------------------------------------------
-// One lane per segment of 2^task.segment_log2 (32..128, one value per launch: plan.h) consecutive
+// One lane per segment of 2^task.segment_log2 (8..128, one value per launch: plan.h) consecutive
 // sorted entries.  The lane walks its entries,
 // gathers each addend from the resident generator array and adds it into a register-resident
 // accumulator; at a bucket boundary the accumulator is flushed.  The lane in whose segment a
@@ -1442,55 +1285,11 @@ template <class P> __device__ __forceinline__ P wave_shfl_down(const P& v, u32 d
   return r;
 }
 
-// wave priorities (s_setprio, 0..3) of the two tail kernels, see k_reduce; BZ_FRONT_PRIO: of the
-// front kernels (conversion, recoding, the sort), 0 = the hardware default, no instruction
-#ifndef BZ_REDUCE_PRIO
-#define BZ_REDUCE_PRIO 3
-#endif
-#ifndef BZ_HORNER_PRIO
-#define BZ_HORNER_PRIO 3
-#endif
-// waves per SIMD the accumulation loop is compiled for: the curve's constant, unless the translation
-// unit that INSTANTIATES the kernel overrides it (blitzar_amd/build.py: the curve25519 loop under a
-// bound of two waves keeps its 140 VGPRs but loses a third of its s_nop padding).  The override only
-// changes an attribute of the kernel's definition; every class constant is the same in every unit.
-#ifdef BZ_ACCUMULATE_WAVES_OVERRIDE
-#define BZ_ACCUMULATE_WAVES(C) (BZ_ACCUMULATE_WAVES_OVERRIDE)
-#else
-#define BZ_ACCUMULATE_WAVES(C) (C::accumulate_waves_per_simd)
-#endif
-// BZ_ACCUMULATE_NT (A/B): bit 0 -- the flushed sums / head partials leave through nontemporal stores
-// (written once here, read once by k_reduce: they need not displace the addend table from the caches);
-// bit 1 -- the sorted entries arrive through nontemporal loads (read once)
-#ifndef BZ_ACCUMULATE_NT
-#define BZ_ACCUMULATE_NT 0
-#endif
-template <class P> __device__ __forceinline__ void store_flushed(P* dst, const P& v) {
-  if constexpr ((BZ_ACCUMULATE_NT & 1) != 0) {
-    typedef u32 vec4 __attribute__((ext_vector_type(4)));
-    const u32* w = reinterpret_cast<const u32*>(&v);
-    u32* d = reinterpret_cast<u32*>(dst);
-    constexpr u32 words = sizeof(P) / 4;
-#pragma unroll
-    for (u32 k = 0; k + 4 <= words; k += 4) {
-      const vec4 piece = {w[k], w[k + 1], w[k + 2], w[k + 3]};
-      __builtin_nontemporal_store(piece, reinterpret_cast<vec4*>(d + k));
-    }
-#pragma unroll
-    for (u32 k = words & ~3u; k < words; ++k) __builtin_nontemporal_store(w[k], d + k);
-  } else {
-    *dst = v;
-  }
-}
-__device__ __forceinline__ u32 load_entry(const u32* p) {
-  if constexpr ((BZ_ACCUMULATE_NT & 2) != 0) {
-    return __builtin_nontemporal_load(p);
-  } else {
-    return *p;
-  }
-}
+// wave priorities (s_setprio, 0..3) of the two tail kernels, see k_reduce
+constexpr int kReducePrio = 3;
+constexpr int kHornerPrio = 3;
 template <class C>
-__global__ void __launch_bounds__(kAccumulateThreads, BZ_ACCUMULATE_WAVES(C))
+__global__ void __launch_bounds__(kAccumulateThreads, C::accumulate_launch_waves)
     k_accumulate(typename C::point* __restrict__ bucket_sums, typename C::point* __restrict__ heads,
                  const u32* __restrict__ bucket_end, const u32* __restrict__ segment_bucket,
                  const u32* __restrict__ sorted, const typename C::addend* __restrict__ addends,
@@ -1499,7 +1298,7 @@ __global__ void __launch_bounds__(kAccumulateThreads, BZ_ACCUMULATE_WAVES(C))
   const u32* ends = bucket_end + task.bucket_base;
   const u32 total = ends[task.num_buckets - 1];
   const u32 seg = blockIdx.x * kAccumulateThreads + threadIdx.x;
-  const u32 seg_entries = 1u << task.segment_log2; // 32, or more for throughput-bound launches
+  const u32 seg_entries = 1u << task.segment_log2; // 8..128 (plan.h, choose_segment_log2)
   const u32 lo = seg << task.segment_log2;
   if (lo >= total) return;
   const u32 hi = lo + seg_entries < total ? lo + seg_entries : total;
@@ -1529,52 +1328,34 @@ __global__ void __launch_bounds__(kAccumulateThreads, BZ_ACCUMULATE_WAVES(C))
   const u32 last_bucket = task.num_buckets - 1;
   u32 next_end = ends[b < last_bucket ? b + 1 : last_bucket];
   typename C::point* flush_to = owned ? sums + b : heads + task.segment_base + seg;
-  u32 e_cur = load_entry(idx + lo);
-  u32 e_next = lo + 1 < hi ? load_entry(idx + lo + 1) : 0;
-  // (curves with C::has_signed_gather fetch the row in the order the digit's sign asks for)
-  // BZ_ACCUMULATE_ROW_MASK (timing experiments only, WRONG results): every gather lands in the first
-  // mask + 1 rows of the table -- what the loop costs when its rows come from the nearest cache
-#ifndef BZ_ACCUMULATE_ROW_MASK
-#define BZ_ACCUMULATE_ROW_MASK 0x7fffffffu
-#endif
+  // (entries are addressed as idx + pos + k: the 64-bit offsets hipcc schedules this loop with)
+  u32 e_cur = *(idx + lo);
+  u32 e_next = lo + 1 < hi ? *(idx + lo + 1) : 0;
+  // an entry is sign << 31 | row (curves with C::has_signed_gather fetch the row in the order the
+  // digit's sign asks for)
   auto gather = [&](u32 entry) {
     if constexpr (C::has_signed_gather) {
-      return C::gather(addends, entry & BZ_ACCUMULATE_ROW_MASK, (entry >> 31) != 0);
+      return C::gather(addends, entry & 0x7fffffffu, (entry >> 31) != 0);
     } else {
-      return addends[entry & BZ_ACCUMULATE_ROW_MASK];
+      return addends[entry & 0x7fffffffu];
     }
   };
-  // BZ_ACCUMULATE_DIRECT=1 (A/B): no row in flight across the addition -- 32 registers fewer, for a
-  // fourth wavefront per SIMD to hide the gather instead
-#ifndef BZ_ACCUMULATE_DIRECT
-#define BZ_ACCUMULATE_DIRECT 0
-#endif
-  // BZ_ACCUMULATE_DIRECT=2 (curves with C::has_split_add): the next row is requested between the two
-  // halves of the addition, where neither the accumulator nor the operand is live
-  constexpr bool kSplit = BZ_ACCUMULATE_DIRECT == 2 && C::has_split_add;
-  constexpr bool kDirect = BZ_ACCUMULATE_DIRECT == 1 || (BZ_ACCUMULATE_DIRECT == 2 && !kSplit);
   typename C::addend staged = gather(e_cur);
   // The first entry of a segment meets the identity in every lane of the wavefront (and never a
   // bucket boundary: `b` is the bucket that holds entry `lo`), so it is loaded, not added:
   // curve25519 one field product instead of eight, the Weierstrass curves none (C::first).
-  // BZ_ACCUMULATE_PEEL=0 keeps the uniform loop (A/B).
-#ifndef BZ_ACCUMULATE_PEEL
-#define BZ_ACCUMULATE_PEEL 1
-#endif
-  u32 first = lo;
-  if constexpr (BZ_ACCUMULATE_PEEL != 0) {
+  {
     const typename C::operand q = C::stage(staged);
     const bool negate = (e_cur >> 31) != 0;
     const u32 next_entry = lo + 1 < hi ? e_next : e_cur;
     e_cur = e_next;
-    if constexpr (!kDirect) staged = gather(next_entry);
-    if (lo + 2 < hi) e_next = load_entry(idx + lo + 2);
+    staged = gather(next_entry);
+    if (lo + 2 < hi) e_next = *(idx + lo + 2);
     if constexpr (C::has_signed_gather) {
       acc = C::first_gathered(q, negate);
     } else {
       acc = C::first(q, negate);
     }
-    first = lo + 1;
     // (materialised here: left to itself hipcc no longer updates the loop's accumulator in place
     // and copies it at the end of every iteration -- curve25519 36 v_mov_b32, 140 -> 179 VGPRs
     // -- C::first_pinned; the Weierstrass loops are better off without)
@@ -1584,16 +1365,15 @@ __global__ void __launch_bounds__(kAccumulateThreads, BZ_ACCUMULATE_WAVES(C))
       for (u32 k = 0; k < sizeof(acc) / 4; ++k) asm volatile("" : "+v"(w[k]));
     }
   }
-  for (u32 i = first; i < hi; ++i) {
+  for (u32 i = lo + 1; i < hi; ++i) {
     // the staged row first: the waits hipcc puts in front of its registers count every memory
     // operation of the wavefront in order, so behind the flush block they would also wait for the
     // block's nine stores to complete (curve25519 k_accumulate 0.629 -> 0.625 ms alone, 0.655 ->
     // 0.648 in a sequence; the Weierstrass kernels unchanged)
-    if constexpr (kDirect) staged = gather(e_cur);
     const typename C::operand q = C::stage(staged);
     const bool negate = (e_cur >> 31) != 0;
     if (i == b_end) {
-      store_flushed(flush_to, acc);
+      *flush_to = acc;
       ++b;
       b_end = next_end;
       while (b_end == i) { // empty buckets
@@ -1610,21 +1390,12 @@ __global__ void __launch_bounds__(kAccumulateThreads, BZ_ACCUMULATE_WAVES(C))
     // copies of the row and moves it back and forth (bn254: 16 v_mov_b64 per iteration)
     const u32 next_entry = i + 1 < hi ? e_next : e_cur;
     e_cur = e_next;
-    if constexpr (kSplit) {
-      const typename C::completed mid = C::add_front(acc, q, negate);
-      asm volatile("" ::: "memory");
-      staged = gather(next_entry);
-      if (i + 2 < hi) e_next = load_entry(idx + i + 2);
-      asm volatile("" ::: "memory");
-      acc = C::add_back(mid);
+    staged = gather(next_entry);
+    if (i + 2 < hi) e_next = *(idx + i + 2);
+    if constexpr (C::has_signed_gather) {
+      C::accumulate_gathered(acc, q, negate);
     } else {
-      if constexpr (!kDirect) staged = gather(next_entry);
-      if (i + 2 < hi) e_next = load_entry(idx + i + 2);
-      if constexpr (C::has_signed_gather) {
-        C::accumulate_gathered(acc, q, negate);
-      } else {
-        C::accumulate(acc, q, negate);
-      }
+      C::accumulate(acc, q, negate);
     }
   }
   // runs of `whole` lanes (necessarily of one bucket) -> one head per run and wavefront
@@ -1639,7 +1410,7 @@ __global__ void __launch_bounds__(kAccumulateThreads, BZ_ACCUMULATE_WAVES(C))
     }
     if (whole && lane != 0 && ((whole_mask >> (lane - 1)) & 1) != 0) write_head = false;
   }
-  if (owned || write_head) store_flushed(flush_to, acc);
+  if (owned || write_head) *flush_to = acc;
 }
 
 // k_accumulate<C> is instantiated in a translation unit of its own per curve
@@ -1738,7 +1509,7 @@ __global__ void __launch_bounds__(T)
   __shared__ point tree[T];
   // a latency chain at one wavefront per SIMD: when it runs beside another batch's k_accumulate
   // (msm_context: throughput mode) its instructions go first, the accumulation fills the slots it leaves
-  __builtin_amdgcn_s_setprio(BZ_REDUCE_PRIO);
+  __builtin_amdgcn_s_setprio(kReducePrio);
   const task_desc task = tasks[blockIdx.y];
   const u32 nb = task.num_buckets;
   const u32 seg_log2 = task.segment_log2; // k_accumulate's segments: where the head partials are
@@ -1910,7 +1681,7 @@ __global__ void __launch_bounds__(kReduceThreads)
                      const task_desc* __restrict__ tasks, u32 lane_log2) {
   using point = typename C::point;
   __shared__ point tree[kReduceThreads];
-  __builtin_amdgcn_s_setprio(BZ_REDUCE_PRIO);
+  __builtin_amdgcn_s_setprio(kReducePrio);
   const task_desc task = tasks[blockIdx.y];
   const u32 nb = task.num_buckets;
   const u32 seg_log2 = task.segment_log2;
@@ -2185,7 +1956,7 @@ __global__ void __launch_bounds__(T)
              u32 w_hi_arg, int first, int last, u32 reduce_block_log2) {
   using point = typename C::point;
   __shared__ point tree[T];
-  __builtin_amdgcn_s_setprio(BZ_HORNER_PRIO); // one workgroup per column, possibly beside k_accumulate
+  __builtin_amdgcn_s_setprio(kHornerPrio); // one workgroup per column, possibly beside k_accumulate
   const column_desc col = columns[blockIdx.x];
   const u32 tid = threadIdx.x;
   u8* dst = out + static_cast<u64>(blockIdx.x) * out_stride;

@@ -9,7 +9,7 @@
 // The digits of a task are sorted by bucket in two passes (kernels.h): the buckets are cut into
 // *groups* of 2^s consecutive buckets, the rows into *slices* (one workgroup each); pass 1
 // partitions every slice's digits by group, pass 2 sorts one group per workgroup inside LDS.  The
-// sorted entry list is then cut into *segments* (32..128 entries, one lane each) for the
+// sorted entry list is then cut into *segments* (8..128 entries, one lane each) for the
 // bucket accumulation, so the parallelism of every stage is proportional to the number of rows
 // and independent of how the digits are distributed over the buckets.
 //
@@ -67,22 +67,13 @@ constexpr u32 kMaxGroupBits = 10;         // 2^s counters of the per-group sort 
 constexpr u32 kMaxGroupsLog2 = 10;        // pass 1 writes one stream per group: keep them few
 
 // buckets a reduce block covers (threads per block x buckets per thread), shared with kernels.h
-#ifndef BZ_REDUCE_THREADS
-#define BZ_REDUCE_THREADS 256
-#endif
-constexpr u32 kReduceThreads = BZ_REDUCE_THREADS;
-#ifndef BZ_REDUCE_SEGMENT_LOG2
-#define BZ_REDUCE_SEGMENT_LOG2 3
-#endif
+constexpr u32 kReduceThreads = 256;
 // buckets per k_reduce lane = 2^s, chosen per launch (msm_plan::reduce_segment_log2): a lane pays
 // 2 additions per bucket plus ~30 per lane (its weight and the tree), so few buckets per lane keep
 // the dependent chain of a latency-bound launch short (one column: s = 3), many buckets per lane
 // keep the total work of a throughput-bound launch small (hundreds of columns: s = 6)
-constexpr u32 kReduceSegmentLog2 = BZ_REDUCE_SEGMENT_LOG2;
-#ifndef BZ_REDUCE_SEGMENT_LOG2_MAX
-#define BZ_REDUCE_SEGMENT_LOG2_MAX 6
-#endif
-constexpr u32 kReduceSegmentLog2Max = BZ_REDUCE_SEGMENT_LOG2_MAX;
+constexpr u32 kReduceSegmentLog2 = 3;
+constexpr u32 kReduceSegmentLog2Max = 6;
 // lanes that fill the machine twice over (1024 SIMDs x 64 lanes x 2 waves)
 constexpr u64 kReduceFillLanes = 131072;
 // `in_sequence`: a call in throughput mode (msm_context).  Its k_reduce runs beside the next call
@@ -204,9 +195,6 @@ struct msm_plan {
   u32 reduce_block_log2() const { return (reduce_threads == 64 ? 6 : 8) + reduce_segment_log2; }
 };
 
-#ifndef BZ_THROUGHPUT_BUCKET_COST
-#define BZ_THROUGHPUT_BUCKET_COST 3.5
-#endif
 struct msm_tuning {
   u32 max_window_bits = 16; // separate windows store their digits as int16 (merged tasks of wide tables: int32)
   // batching of many-column jobs: tasks per launch (grid.y) and device workspace per batch
@@ -216,7 +204,7 @@ struct msm_tuning {
   u32 partition_group_entries = kGroupTargetEntries;
   // window-width cost model: from this many columns on, buckets cost `throughput_bucket_cost`
   size_t throughput_columns = 4;
-  double throughput_bucket_cost = BZ_THROUGHPUT_BUCKET_COST;
+  double throughput_bucket_cost = 3.5;
   u32 force_window_bits = 0;         // tests (bzamd_set_window_bits): this width wherever a column allows it
   bool in_sequence = false; // set per call by msm_enqueue: the call runs in throughput mode
   // wavefronts of k_accumulate the device holds at once (waves per SIMD of the curve's loop x SIMDs;
