@@ -353,26 +353,61 @@ SUMCHECK_CALLBACK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p, cty
 SUMCHECK_PRODUCT_STRIDE = {0: 36, 1: 40}  # std::pair<FIELD, unsigned> of the reference
 
 
-def prove_sumcheck(field_id, mles, product_table, product_terms, n, round_degree, callback):
-    """sxt_prove_sumcheck.  mles: uint8 [num_mles, n, 32]; product_table: raw bytes of
-    num_products x {32-byte multiplier; unsigned length}; callback(r_ptr, ctx, poly_ptr, length).
-    -> (polynomials [num_variables, round_degree + 1, 32], evaluation_point [num_variables, 32])"""
-    m = np.ascontiguousarray(mles, dtype=np.uint8)
+def _sumcheck_call(symbol, field_id, mles_ptr, num_mles, product_table, product_terms, n,
+                   round_degree, callback, with_evaluations, stream=None):
     table = np.ascontiguousarray(product_table, dtype=np.uint8)
     terms = np.ascontiguousarray(product_terms, dtype=np.uint32)
     num_variables = max((int(n) - 1).bit_length(), 1)
     polys = np.zeros((num_variables, round_degree + 1, 32), dtype=np.uint8)
     point = np.zeros((num_variables, 32), dtype=np.uint8)
-    d = sumcheck_descriptor(m.ctypes.data, table.ctypes.data, terms.ctypes.data, n, m.shape[0],
+    d = sumcheck_descriptor(mles_ptr, table.ctypes.data, terms.ctypes.data, n, num_mles,
                             table.size // SUMCHECK_PRODUCT_STRIDE[field_id], terms.size,
                             round_degree)
     cb = SUMCHECK_CALLBACK(callback)
-    fn = load().sxt_prove_sumcheck
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint,
-                   ctypes.POINTER(sumcheck_descriptor), SUMCHECK_CALLBACK, ctypes.c_void_p]
+    vp = ctypes.c_void_p
+    fn = getattr(load(), symbol)
     fn.restype = None
-    fn(_ptr(polys), _ptr(point), field_id, ctypes.byref(d), cb, None)
-    return polys, point
+    tail = [ctypes.c_uint, ctypes.POINTER(sumcheck_descriptor), SUMCHECK_CALLBACK, vp]
+    if not with_evaluations:
+        fn.argtypes = [vp, vp] + tail
+        fn(_ptr(polys), _ptr(point), field_id, ctypes.byref(d), cb, None)
+        return polys, point
+    evaluations = np.zeros((num_mles, 32), dtype=np.uint8)
+    if symbol == "bzamd_prove_sumcheck_device":
+        fn.argtypes = [vp, vp, vp] + tail + [vp]
+        fn(_ptr(polys), _ptr(point), _ptr(evaluations), field_id, ctypes.byref(d), cb, None, stream)
+    else:
+        fn.argtypes = [vp, vp, vp] + tail
+        fn(_ptr(polys), _ptr(point), _ptr(evaluations), field_id, ctypes.byref(d), cb, None)
+    return polys, point, evaluations
+
+
+def prove_sumcheck(field_id, mles, product_table, product_terms, n, round_degree, callback):
+    """sxt_prove_sumcheck.  mles: uint8 [num_mles, n, 32]; product_table: raw bytes of
+    num_products x {32-byte multiplier; unsigned length}; callback(r_ptr, ctx, poly_ptr, length).
+    -> (polynomials [num_variables, round_degree + 1, 32], evaluation_point [num_variables, 32])"""
+    m = np.ascontiguousarray(mles, dtype=np.uint8)
+    return _sumcheck_call("sxt_prove_sumcheck", field_id, m.ctypes.data, m.shape[0], product_table,
+                          product_terms, n, round_degree, callback, False)
+
+
+def prove_sumcheck_with_evaluations(field_id, mles, product_table, product_terms, n, round_degree,
+                                    callback):
+    """bzamd_prove_sumcheck: prove_sumcheck plus mle_evaluations [num_mles, 32], the value of every
+    MLE at the evaluation point -> (polynomials, evaluation_point, mle_evaluations)"""
+    m = np.ascontiguousarray(mles, dtype=np.uint8)
+    return _sumcheck_call("bzamd_prove_sumcheck", field_id, m.ctypes.data, m.shape[0],
+                          product_table, product_terms, n, round_degree, callback, True)
+
+
+def prove_sumcheck_device(field_id, mles_device_ptr, num_mles, product_table, product_terms, n,
+                          round_degree, callback, stream=None):
+    """bzamd_prove_sumcheck_device: the tables ([num_mles, n, 32] bytes) are device memory of the
+    current device at `mles_device_ptr`, `stream` a hipStream_t as an integer (None: the default
+    stream); everything else on the host -> (polynomials, evaluation_point, mle_evaluations)"""
+    return _sumcheck_call("bzamd_prove_sumcheck_device", field_id, int(mles_device_ptr), num_mles,
+                          product_table, product_terms, n, round_degree, callback, True,
+                          None if stream is None else ctypes.c_void_p(int(stream)))
 
 
 class MultiexpHandle:

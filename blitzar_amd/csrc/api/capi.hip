@@ -1585,26 +1585,65 @@ int sxt_curve25519_verify_inner_product(struct sxt_transcript* transcript, uint6
              : 0;
 }
 
-void sxt_prove_sumcheck(void* polynomials, void* evaluation_point, unsigned field_id,
-                        const struct sumcheck_descriptor* descriptor, void* transcript_callback,
-                        void* transcript_context) {
-  BZ_RELEASE_ASSERT(polynomials != nullptr && evaluation_point != nullptr && descriptor != nullptr &&
-                        transcript_callback != nullptr,
-                    "null argument to `sxt_prove_sumcheck`");
+namespace {
+// sxt_prove_sumcheck and bzamd_prove_sumcheck* (`name`: the entry point, for the messages);
+// `device_form`: descriptor->mles is memory of the current device, the kernels go on `stream`
+void prove_sumcheck_entry(const char* name, void* polynomials, void* evaluation_point,
+                          void* mle_evaluations, unsigned field_id,
+                          const struct sumcheck_descriptor* descriptor, void* transcript_callback,
+                          void* transcript_context, bool device_form, void* stream) {
+  if (polynomials == nullptr || evaluation_point == nullptr || descriptor == nullptr ||
+      transcript_callback == nullptr) {
+    std::fprintf(stderr, "blitzar_amd: null argument to `%s`\n", name);
+    std::abort();
+  }
   BZ_RELEASE_ASSERT(descriptor->mles != nullptr && descriptor->product_table != nullptr &&
                         descriptor->product_terms != nullptr,
                     "null table in the sumcheck descriptor");
   api_state& st = state();
-  // devices[0] is held while the prover works on it and given up around every call of the caller's
-  // transcript callback, which may therefore call back into this library (the tables of the proof
-  // live in memory of the call's own, not in the device's staging arena)
-  api_state::device_lease lease = lease_primary(st);
   const proof::sumcheck_inputs in{descriptor->mles,         descriptor->product_table,
                                   descriptor->product_terms, descriptor->n,
                                   descriptor->num_mles,      descriptor->num_products,
                                   descriptor->num_product_terms, descriptor->round_degree};
-  proof::prove_sumcheck(st, polynomials, evaluation_point, field_id, in, transcript_callback,
-                        transcript_context, &lease);
+  if (device_form) {
+    // the current device, the caller's stream, memory of the call's own: none of the backend's
+    // per-device state is touched, so no lease is taken and the callback may call back freely
+    BZ_RELEASE_ASSERT(st.backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
+    proof::sumcheck_device_tables tables{0, static_cast<hipStream_t>(stream)};
+    BZ_HIP_CHECK(hipGetDevice(&tables.device));
+    proof::prove_sumcheck(st, polynomials, evaluation_point, mle_evaluations, field_id, in,
+                          transcript_callback, transcript_context, nullptr, &tables);
+    return;
+  }
+  // devices[0] is held while the prover works on it and given up around every call of the caller's
+  // transcript callback, which may therefore call back into this library (the tables of the proof
+  // live in memory of the call's own, not in the device's staging arena)
+  api_state::device_lease lease = lease_primary(st);
+  proof::prove_sumcheck(st, polynomials, evaluation_point, mle_evaluations, field_id, in,
+                        transcript_callback, transcript_context, &lease);
+}
+} // namespace
+
+void sxt_prove_sumcheck(void* polynomials, void* evaluation_point, unsigned field_id,
+                        const struct sumcheck_descriptor* descriptor, void* transcript_callback,
+                        void* transcript_context) {
+  prove_sumcheck_entry("sxt_prove_sumcheck", polynomials, evaluation_point, nullptr, field_id,
+                       descriptor, transcript_callback, transcript_context, false, nullptr);
+}
+
+void bzamd_prove_sumcheck(void* polynomials, void* evaluation_point, void* mle_evaluations,
+                          unsigned field_id, const struct sumcheck_descriptor* descriptor,
+                          void* transcript_callback, void* transcript_context) {
+  prove_sumcheck_entry("bzamd_prove_sumcheck", polynomials, evaluation_point, mle_evaluations,
+                       field_id, descriptor, transcript_callback, transcript_context, false, nullptr);
+}
+
+void bzamd_prove_sumcheck_device(void* polynomials, void* evaluation_point, void* mle_evaluations,
+                                 unsigned field_id, const struct sumcheck_descriptor* descriptor,
+                                 void* transcript_callback, void* transcript_context, void* stream) {
+  prove_sumcheck_entry("bzamd_prove_sumcheck_device", polynomials, evaluation_point,
+                       mle_evaluations, field_id, descriptor, transcript_callback,
+                       transcript_context, true, stream);
 }
 
 //--------------------------------------------------------------------------------------------------

@@ -270,6 +270,30 @@ void bzamd_fixed_packed_multiexponentiation_device(void* res, const struct sxt_m
                                                    unsigned num_outputs, unsigned n,
                                                    const uint8_t* scalars, void* stream);
 
+/* Sumcheck prover (sxt_prove_sumcheck) that also returns what the caller sends the verifier next,
+ * and its form on device-resident tables.  `polynomials`, `evaluation_point`, the descriptor and
+ * the transcript callback are those of sxt_prove_sumcheck, and with the same inputs the same bytes
+ * are written to them; limits and aborts are the same (round_degree <= 8, n <= 2^30).
+ * `mle_evaluations` (may be NULL): num_mles field elements in the caller's representation,
+ * canonical: mle_evaluations[j] = f_j(r_1 .. r_v), the value of MLE j at the evaluation point.
+ * With v = max(ceil_log2(n), 1), T_0 = the tables padded with zero rows to 2^v, mid_t = 2^(v-1-t) and
+ *   T_{t+1}[j][i] = (1 - r_t) T_t[j][i] + r_t T_t[j][mid_t + i],
+ * it is T_v[j][0]: the fold the prover does between rounds, applied once more with the last
+ * challenge (n = 1: (1 - r_0) f_j[0]). */
+/* HOST operands, blocking, cpu and gpu backends */
+void bzamd_prove_sumcheck(void* polynomials, void* evaluation_point, void* mle_evaluations,
+                          unsigned field_id, const struct sumcheck_descriptor* descriptor,
+                          void* transcript_callback, void* transcript_context);
+/* descriptor->mles is a DEVICE pointer on the current HIP device; everything else is HOST.  gpu
+ * backend only.  Blocking (the transcript callback runs on the host every round).  The tables are
+ * read in stream order after the work already enqueued on `stream` and are not modified; when the
+ * call returns, all reads of them are complete.  The kernels run on `stream`, the working tables
+ * live in device memory of the call's own, and no device of the backend is held: the callback may
+ * call back into the library. */
+void bzamd_prove_sumcheck_device(void* polynomials, void* evaluation_point, void* mle_evaluations,
+                                 unsigned field_id, const struct sumcheck_descriptor* descriptor,
+                                 void* transcript_callback, void* transcript_context, void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

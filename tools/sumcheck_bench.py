@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Sumcheck prover, warm, on one GPU: the arguments and the workload of the reference's
+benchmark/sumcheck/benchmark.m.cc (degree x num_products random MLEs of n rows, every product of
+length `degree`, a hash transcript), for both fields of the ABI.
+
+    python tools/sumcheck_bench.py <n> <degree> <num_products> <num_samples> [--fields 0,1]
+
+Timed, with a device synchronise inside the clock, after one untimed call:
+  host    sxt_prove_sumcheck: the tables start in host memory (their upload is part of the call);
+  device  bzamd_prove_sumcheck_device: the tables are resident in HBM before the clock starts.
+The transcript callback is Python (one ctypes call and one SHA-256 per round); its cost is timed
+alone and printed beside the two (`callback_ms`) -- it is inside both figures and is not kernel time.
+BLITZAR_AMD_LIB selects the library (A/B against another build in one session); a library without
+bzamd_prove_sumcheck_device reports the device leg as absent.  Prints one JSON line.  Needs a GPU:
+there is no CPU fallback."""
+import argparse
+import ctypes
+import hashlib
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch  # (before the library: torch's HIP runtime first, tests/conftest.py)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from blitzar_amd import api  # noqa: E402
+
+MODULUS = {0: 2**252 + 27742317777372353535851937790883648493,
+           1: 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001}
+TOP_BYTE_MASK = {0: 0x0f, 1: 0x1f}  # below the modulus: canonical in either representation
+
+
+def random_elements(rng, field_id, count):
+    out = rng.integers(0, 256, (count, 32), dtype=np.uint8)
+    out[:, 31] &= TOP_BYTE_MASK[field_id]
+    return out
+
+
+def hash_callback(field_id):
+    p = MODULUS[field_id]
+
+    def cb(r_ptr, ctx, poly_ptr, length):
+        poly = ctypes.string_at(poly_ptr, 32 * length)
+        v = int.from_bytes(hashlib.sha256(poly).digest(), "little") % p
+        ctypes.memmove(r_ptr, v.to_bytes(32, "little"), 32)
+    return cb
+
+
+def samples_ms(fn, num_samples):
+    fn()  # warm
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(num_samples):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return out
+
+
+def summary(ms):
+    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4),
+            "max_ms": round(max(ms), 4), "samples_ms": [round(x, 4) for x in ms]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("n", type=int)
+    ap.add_argument("degree", type=int)
+    ap.add_argument("num_products", type=int)
+    ap.add_argument("num_samples", type=int)
+    ap.add_argument("--fields", default="0,1")
+    args = ap.parse_args()
+    lib = api.load()
+    assert lib.bzamd_device_count() > 0, "sumcheck_bench needs a GPU"
+    api.reset_for_testing()
+    assert api.init(api.SXT_GPU_BACKEND, 0) == 0
+    dev = torch.device("cuda", 0)
+    has_device_form = hasattr(lib, "bzamd_prove_sumcheck_device")
+    n, degree, num_products = args.n, args.degree, args.num_products
+    num_mles = degree * num_products
+    rounds = max((n - 1).bit_length(), 1)
+    rec = {"n": n, "degree": degree, "num_products": num_products, "num_mles": num_mles,
+           "rounds": rounds, "num_samples": args.num_samples, "library": api.LIB_PATH,
+           "table_bytes": 32 * n * num_mles, "fields": {}}
+    for field_id in (int(x) for x in args.fields.split(",")):
+        rng = np.random.default_rng(1 + field_id)
+        mles = random_elements(rng, field_id, n * num_mles).reshape(num_mles, n, 32)
+        stride = api.SUMCHECK_PRODUCT_STRIDE[field_id]
+        table = np.zeros((num_products, stride), np.uint8)
+        table[:, :32] = random_elements(rng, field_id, num_products)
+        table[:, 32:36] = np.frombuffer(np.uint32(degree).tobytes(), np.uint8)
+        terms = np.arange(num_mles, dtype=np.uint32)
+        cb = hash_callback(field_id)
+        out = {}
+
+        def host():
+            out["host"] = api.prove_sumcheck(field_id, mles, table, terms, n, degree, cb)
+
+        result = {"host": summary(samples_ms(host, args.num_samples))}
+        if has_device_form:
+            d_mles = torch.from_numpy(mles).to(dev)
+            torch.cuda.synchronize()
+
+            def device():
+                out["device"] = api.prove_sumcheck_device(field_id, d_mles.data_ptr(), num_mles,
+                                                          table, terms, n, degree, cb)
+
+            result["device"] = summary(samples_ms(device, args.num_samples))
+            result["device_saves_upload_bytes"] = rec["table_bytes"]
+            same = all(np.array_equal(a, b) for a, b in zip(out["host"], out["device"][:2]))
+            result["device_equals_host"] = bool(same)
+            assert same, "the device form disagrees with sxt_prove_sumcheck"
+        else:
+            result["device"] = "absent"
+        # the Python transcript alone: `rounds` calls through ctypes, as the prover makes them
+        c_cb = api.SUMCHECK_CALLBACK(cb)
+        poly = np.ascontiguousarray(out["host"][0][0])
+        r = np.zeros(32, np.uint8)
+        t0 = time.perf_counter()
+        for _ in range(10 * rounds):
+            c_cb(r.ctypes.data, None, poly.ctypes.data, degree + 1)
+        result["callback_ms"] = round((time.perf_counter() - t0) * 1e3 / 10, 4)
+        result["polynomials_sha256"] = hashlib.sha256(out["host"][0].tobytes()).hexdigest()[:16]
+        rec["fields"][str(field_id)] = result
+    print(json.dumps(rec), flush=True)
+
+
+if __name__ == "__main__":
+    main()
