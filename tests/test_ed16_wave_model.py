@@ -3,8 +3,9 @@ algorithm -- limb layout, rotations with the 2^256 = 38 wrap, carry rounds, the 
 the limb-wise multiples of p used for subtraction -- is restated in tools/models/ed16_wave_model.py
 with interval propagation of every limb bound.  This runs the model: values against big-integer
 edwards25519 arithmetic, bounds against the 24-bit / 32-bit / 48-bit / 64-bit limits of the
-instructions the kernel uses.  (The kernel itself is covered by every -m gpu parity test: all MSM
-results pass through it.)"""
+instructions the kernel uses.  (That the kernel computes what this model says is checked lane for
+lane, on the GPU, by tests/test_device_arith.py through the model's run_fmul / run_dbl /
+run_add_cached accessors; every -m gpu parity test passes through the kernel as well.)"""
 import importlib.util
 import os
 

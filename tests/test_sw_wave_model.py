@@ -6,8 +6,9 @@ the limb-wise multiple of p used for subtraction -- is restated in tools/models/
 interval propagation of every limb bound.  This runs the model for the three base fields: values
 against big-integer arithmetic (products, a doubling / addition chain, the special cases of the
 complete formulas), bounds against the 32-bit / 64-bit limits of the instructions the kernel uses.
-(The kernel itself is covered by every -m gpu parity test on bn254 / grumpkin / bls12-381: all their
-MSM results pass through it.)"""
+(That the kernel computes what this model says is checked lane for lane, on the GPU, by
+tests/test_device_arith.py through the model's run_fmul / run_dbl / run_add accessors; every -m gpu
+parity test on bn254 / grumpkin / bls12-381 passes through the kernel as well.)"""
 import importlib.util
 import os
 

@@ -138,6 +138,17 @@ def check_point_chain():
     return math.log2(max(acc.bnd))
 
 
+# ---- accessors: the lane program on given lane words (tests/test_device_arith.py compares the
+# kernel's 64 output lane words with these).  Bounds start at the values themselves, so the checks
+# above assert that THESE operands stay inside every instruction limit.
+def lanes(words):
+    assert len(words) == L
+    return V([int(w) for w in words], [int(w) for w in words])
+def run_fmul(u, v): return fmul(lanes(u), lanes(v)).val
+def run_dbl(state): return dbl(lanes(state)).val
+def run_add_cached(state, cached): return add_cached(lanes(state), lanes(cached)).val
+
+
 if __name__ == '__main__':
     print('field products ok; limb bounds (bits): limb 0 %.3f, others %.3f' % check_field_products())
     print('6 x (add, 16 doublings) ok; state limb bound %.4f bits' % check_point_chain())

@@ -488,6 +488,28 @@ def check_point_chain(name, doublings=40, seed=3):
     return worst_limb / (f.mask + 1)
 
 
+#------------------------------------------------------------------------------------------------
+# accessors: the lane program on given lane words (tests/test_device_arith.py compares the kernel's 64
+# output lane words with these).  Bounds start at the values themselves, so every check above
+# asserts that THESE operands stay inside the limits of the lane program.
+#------------------------------------------------------------------------------------------------
+def lanes(words):
+    assert len(words) == L
+    return V([int(w) for w in words], [int(w) for w in words])
+
+
+def run_fmul(name, u, v):
+    return Wave(FIELDS[name]).mul(lanes(u), [0, 1, 2, 3], lanes(v)).val
+
+
+def run_dbl(name, state):
+    return dbl(Wave(FIELDS[name]), lanes(state)).val
+
+
+def run_add(name, state, q):
+    return add(Wave(FIELDS[name]), lanes(state), lanes(q)).val
+
+
 def main():
     for name in FIELDS:
         print(name, "product limbs / 2^LB <=", check_field_products(name))
