@@ -177,6 +177,7 @@ def load():
     lib.bzamd_set_shard_min_bytes.argtypes = [u64]
     lib.bzamd_set_shard_min_bytes.restype = None
     lib.bzamd_accumulate_form.restype = ctypes.c_int
+    lib.bzamd_sumcheck_device_bytes.restype = ctypes.c_uint64
     _lib = lib
     return lib
 
@@ -408,6 +409,72 @@ def prove_sumcheck_device(field_id, mles_device_ptr, num_mles, product_table, pr
     return _sumcheck_call("bzamd_prove_sumcheck_device", field_id, int(mles_device_ptr), num_mles,
                           product_table, product_terms, n, round_degree, callback, True,
                           None if stream is None else ctypes.c_void_p(int(stream)))
+
+
+class bzamd_sumcheck_columns(ctypes.Structure):
+    _fields_ = [("mles", ctypes.POINTER(sxt_sequence_descriptor)),
+                ("product_table", ctypes.c_void_p), ("product_terms", ctypes.c_void_p),
+                ("n", ctypes.c_uint), ("num_mles", ctypes.c_uint), ("num_products", ctypes.c_uint),
+                ("num_product_terms", ctypes.c_uint), ("round_degree", ctypes.c_uint)]
+
+
+def _sumcheck_columns_call(symbol, field_id, descs, num_mles, product_table, product_terms, n,
+                           round_degree, callback, stream=None):
+    table = np.ascontiguousarray(product_table, dtype=np.uint8)
+    terms = np.ascontiguousarray(product_terms, dtype=np.uint32)
+    num_variables = max((int(n) - 1).bit_length(), 1)
+    polys = np.zeros((num_variables, round_degree + 1, 32), dtype=np.uint8)
+    point = np.zeros((num_variables, 32), dtype=np.uint8)
+    evaluations = np.zeros((num_mles, 32), dtype=np.uint8)
+    c = bzamd_sumcheck_columns(descs, table.ctypes.data, terms.ctypes.data, n, num_mles,
+                               table.size // SUMCHECK_PRODUCT_STRIDE[field_id], terms.size,
+                               round_degree)
+    cb = SUMCHECK_CALLBACK(callback)
+    vp = ctypes.c_void_p
+    fn = getattr(load(), symbol)
+    fn.restype = None
+    fn.argtypes = [vp, vp, vp, ctypes.c_uint, ctypes.POINTER(bzamd_sumcheck_columns),
+                   SUMCHECK_CALLBACK, vp]
+    args = [_ptr(polys), _ptr(point), _ptr(evaluations), field_id, ctypes.byref(c), cb, None]
+    if symbol == "bzamd_prove_sumcheck_device_columns":
+        fn.argtypes = fn.argtypes + [vp]
+        args.append(stream)
+    fn(*args)
+    return polys, point, evaluations
+
+
+def prove_sumcheck_columns(field_id, columns, product_table, product_terms, n, round_degree,
+                           callback):
+    """bzamd_prove_sumcheck_columns.  columns: one per MLE, a 1-D numpy integer array (its itemsize
+    is the width, a signed dtype a signed column) or a uint8 [rows, nbytes] array (unsigned
+    integers of nbytes, field elements for nbytes = 32), or an (array, is_signed) pair that says
+    it outright; at most n rows each, the rest is zero
+    -> (polynomials, evaluation_point, mle_evaluations)"""
+    pairs = []
+    for c in columns:
+        if isinstance(c, tuple):
+            pairs.append((np.ascontiguousarray(c[0]), bool(c[1])))
+        else:
+            c = np.ascontiguousarray(c)
+            pairs.append((c, c.ndim == 1 and np.issubdtype(c.dtype, np.signedinteger)))
+    descs, keep = make_descriptors(pairs)
+    return _sumcheck_columns_call("bzamd_prove_sumcheck_columns", field_id, descs, len(keep),
+                                  product_table, product_terms, n, round_degree, callback)
+
+
+def prove_sumcheck_device_columns(field_id, descriptors, product_table, product_terms, n,
+                                  round_degree, callback, stream=None):
+    """bzamd_prove_sumcheck_device_columns.  descriptors: one (device_ptr, n_j, nbytes, signed) per
+    MLE, memory of the current device; `stream` a hipStream_t as an integer (None: the default
+    stream); everything else on the host -> (polynomials, evaluation_point, mle_evaluations)"""
+    ds = list(descriptors)
+    descs = (sxt_sequence_descriptor * max(1, len(ds)))()
+    for i, (ptr, rows, nbytes, signed) in enumerate(ds):
+        descs[i] = sxt_sequence_descriptor(nbytes, rows, int(ptr) if rows > 0 else None,
+                                           1 if signed else 0)
+    return _sumcheck_columns_call("bzamd_prove_sumcheck_device_columns", field_id, descs, len(ds),
+                                  product_table, product_terms, n, round_degree, callback,
+                                  None if stream is None else ctypes.c_void_p(int(stream)))
 
 
 class MultiexpHandle:

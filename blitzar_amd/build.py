@@ -33,6 +33,7 @@ SOURCES = [
     "generators/builtin.hip",
     "proof/inner_product.hip",
     "proof/sumcheck.hip",
+    "proof/sumcheck_columns.hip",
     "api/capi.hip",
 ]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-I" + ROOT,

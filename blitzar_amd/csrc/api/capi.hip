@@ -1646,6 +1646,73 @@ void bzamd_prove_sumcheck_device(void* polynomials, void* evaluation_point, void
                        transcript_context, true, stream);
 }
 
+namespace {
+// bzamd_prove_sumcheck_columns / _device_columns; the descriptors are checked by the rule of the
+// MSM entry points (check_descriptors), so one array serves both
+void prove_sumcheck_columns_entry(const char* name, void* polynomials, void* evaluation_point,
+                                  void* mle_evaluations, unsigned field_id,
+                                  const struct bzamd_sumcheck_columns* columns,
+                                  void* transcript_callback, void* transcript_context,
+                                  bool device_form, void* stream) {
+  if (polynomials == nullptr || evaluation_point == nullptr || columns == nullptr ||
+      transcript_callback == nullptr) {
+    std::fprintf(stderr, "blitzar_amd: null argument to `%s`\n", name);
+    std::abort();
+  }
+  BZ_RELEASE_ASSERT(columns->product_table != nullptr && columns->product_terms != nullptr,
+                    "null table in the sumcheck descriptor");
+  BZ_RELEASE_ASSERT(columns->num_mles == 0 || columns->mles != nullptr, "descriptors is null");
+  std::vector<proof::sumcheck_column> cols(columns->num_mles);
+  for (u32 j = 0; j < columns->num_mles; ++j) {
+    const sxt_sequence_descriptor& d = columns->mles[j];
+    BZ_RELEASE_ASSERT(d.n == 0 || d.data != nullptr, "descriptor has n > 0 but null data");
+    BZ_RELEASE_ASSERT(d.element_nbytes != 0 && d.element_nbytes <= 32,
+                      "element_nbytes must be in [1, 32]");
+    BZ_RELEASE_ASSERT(!d.is_signed || d.element_nbytes <= 16,
+                      "signed sequences need element_nbytes <= 16");
+    cols[j] = proof::sumcheck_column{d.data, d.n, d.element_nbytes, d.is_signed != 0};
+  }
+  api_state& st = state();
+  const proof::sumcheck_inputs in{nullptr,           columns->product_table,
+                                  columns->product_terms, columns->n,
+                                  columns->num_mles, columns->num_products,
+                                  columns->num_product_terms, columns->round_degree};
+  if (device_form) {
+    // as bzamd_prove_sumcheck_device: the current device, the caller's stream, no lease
+    BZ_RELEASE_ASSERT(st.backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
+    proof::sumcheck_device_tables tables{0, static_cast<hipStream_t>(stream)};
+    BZ_HIP_CHECK(hipGetDevice(&tables.device));
+    proof::prove_sumcheck_columns(st, polynomials, evaluation_point, mle_evaluations, field_id, in,
+                                  cols.data(), transcript_callback, transcript_context, nullptr,
+                                  &tables);
+    return;
+  }
+  api_state::device_lease lease = lease_primary(st);
+  proof::prove_sumcheck_columns(st, polynomials, evaluation_point, mle_evaluations, field_id, in,
+                                cols.data(), transcript_callback, transcript_context, &lease);
+}
+} // namespace
+
+void bzamd_prove_sumcheck_columns(void* polynomials, void* evaluation_point, void* mle_evaluations,
+                                  unsigned field_id, const struct bzamd_sumcheck_columns* columns,
+                                  void* transcript_callback, void* transcript_context) {
+  prove_sumcheck_columns_entry("bzamd_prove_sumcheck_columns", polynomials, evaluation_point,
+                               mle_evaluations, field_id, columns, transcript_callback,
+                               transcript_context, false, nullptr);
+}
+
+void bzamd_prove_sumcheck_device_columns(void* polynomials, void* evaluation_point,
+                                         void* mle_evaluations, unsigned field_id,
+                                         const struct bzamd_sumcheck_columns* columns,
+                                         void* transcript_callback, void* transcript_context,
+                                         void* stream) {
+  prove_sumcheck_columns_entry("bzamd_prove_sumcheck_device_columns", polynomials, evaluation_point,
+                               mle_evaluations, field_id, columns, transcript_callback,
+                               transcript_context, true, stream);
+}
+
+uint64_t bzamd_sumcheck_device_bytes(void) { return proof::g_sumcheck_arena_bytes.load(); }
+
 //--------------------------------------------------------------------------------------------------
 // extensions (include/blitzar_amd.h)
 //--------------------------------------------------------------------------------------------------

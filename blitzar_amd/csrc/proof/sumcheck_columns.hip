@@ -1,0 +1,340 @@
+// Sumcheck over typed columns (bzamd_prove_sumcheck_columns / _device_columns): the MLEs are the
+// columns a service holds and commits -- little-endian integers of 1 .. 31 bytes, signed up to 16,
+// or 32-byte field elements, each with its own length -- described by the MSM's descriptors.
+//
+// The prover is the one of proof/sumcheck.hip.  What differs is where round 0 and the first fold
+// read: the columns where they lie (k_sumcheck_columns_round, k_sumcheck_columns_generic,
+// k_sumcheck_columns_fold).  No engine-form copy of the full tables exists on the device; from
+// round 1 on the kernels of proof/sumcheck.hip run on the folded half.
+//
+// Neither kernel converts an element.  With R the engine's Montgomery radix, a loaded element is
+// the RAW residue of its bytes: x itself for an integer or a curve25519 scalar, x 2^256 for a
+// Grumpkin element, where the engine form is x R.  A Montgomery product with a raw factor comes out
+// short of one conversion constant c (raw c / R = engine form: R^2, or R^2 / 2^256), and sums and
+// differences do not care.  So round 0 multiplies every product's multiplier by the constants of
+// its terms' columns, once on the host, and then runs the row arithmetic on raw a_j and b_j; the
+// fold multiplies raw rows by r c / R and (1 - r) c / R, which lands in engine form.
+// The host form on the GPU backend uploads the columns at their own width and takes the same path;
+// the host backend converts while it loads its tables.
+#include <cstring>
+#include <vector>
+
+#include "blitzar_amd/csrc/proof/sumcheck_rows.h"
+
+namespace bz::proof {
+namespace {
+// how an element's bytes are fetched (the same for a whole column: uniform over a wavefront)
+enum : u32 {
+  kAccessBytes = 0, // any width, any address
+  kAccessWords = 1, // width a multiple of 8 at an address that is one
+};
+
+struct column_view {
+  const u8* data;
+  u64 n;
+  u32 nbytes, access, is_signed, reserved;
+};
+
+u32 access_of(const void* data, u32 nbytes) {
+  return nbytes % 8 == 0 && reinterpret_cast<uintptr_t>(data) % 8 == 0 ? kAccessWords : kAccessBytes;
+}
+
+// w = the little-endian integer of the c.nbytes bytes at p
+BZ_HD void load_bytes(u64* w, const column_view& c, const u8* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  // the aligned 32-bit words the bytes lie in (never more memory than those: nothing outside the
+  // words that hold a byte of the column is touched), shifted into place and cut to the width;
+  // every array index is a constant, so the words stay in registers
+  const u64 address = reinterpret_cast<u64>(p);
+  const u32 offset = static_cast<u32>(address & 3);
+  const u32* q = reinterpret_cast<const u32*>(address - offset);
+  u32 d[9];
+#pragma unroll
+  for (u32 k = 0; k < 9; ++k) d[k] = 4 * k < offset + c.nbytes ? q[k] : 0;
+#pragma unroll
+  for (u32 k = 0; k < 8; ++k) {
+    u32 x = __builtin_amdgcn_alignbyte(d[k + 1], d[k], offset);
+    const u32 have = c.nbytes > 4 * k ? c.nbytes - 4 * k : 0;
+    if (have < 4) x &= (1u << (8 * have)) - 1;
+    if (k % 2 == 0) {
+      w[k / 2] = x;
+    } else {
+      w[k / 2] |= static_cast<u64>(x) << 32;
+    }
+  }
+#else
+  for (u32 k = 0; k < c.nbytes; ++k) w[k >> 3] |= static_cast<u64>(p[k]) << (8 * (k & 7));
+#endif
+}
+
+// w = magnitude of row i < c.n of the column (little-endian words); returns its sign
+BZ_HD bool load_magnitude(u64* w, const column_view& c, u64 i) {
+  const u8* p = c.data + i * c.nbytes;
+  if (c.access == kAccessWords) {
+    const u64* q = reinterpret_cast<const u64*>(p);
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) {
+      if (8 * k < c.nbytes) w[k] = q[k];
+    }
+  } else {
+    load_bytes(w, c, p);
+  }
+  if (c.is_signed == 0) return false;
+  // at most 16 bytes: sign-extend to 128 bits, take the magnitude
+  u64 lo = w[0], hi = w[1];
+  if (c.nbytes <= 8) {
+    const u32 s = 64 - 8 * c.nbytes;
+    lo = static_cast<u64>(static_cast<i64>(lo << s) >> s);
+    hi = static_cast<u64>(static_cast<i64>(lo) >> 63);
+  } else {
+    const u32 s = 128 - 8 * c.nbytes;
+    hi = static_cast<u64>(static_cast<i64>(hi << s) >> s);
+  }
+  const bool negative = static_cast<i64>(hi) < 0;
+  if (negative) {
+    lo = ~lo + 1;
+    hi = ~hi + (lo == 0 ? 1 : 0);
+  }
+  w[0] = lo;
+  w[1] = hi;
+  return negative;
+}
+
+// row i < c.n as the raw residue of its bytes, normalised, V < 4 (32 bytes may hold up to 16 p)
+template <class F> BZ_HD typename F::fe load_raw(const column_view& c, u64 i) {
+  u64 w[4] = {0, 0, 0, 0};
+  const bool negative = load_magnitude(w, c, i);
+  const typename F::fe v = F::reduce(F::from_words(w));
+  return F::select(v, fneg<F>(v), negative);
+}
+
+// row i < c.n in engine form (the host backend's tables)
+template <class E> typename E::F::fe load_element(const column_view& c, u64 i) {
+  using F = typename E::F;
+  u64 w[4] = {0, 0, 0, 0};
+  const bool negative = load_magnitude(w, c, i);
+  const typename F::fe v = E::convert(w, c.nbytes == E::element_bytes);
+  return F::select(v, fneg<F>(v), negative);
+}
+
+// the `Tables` of round 0 (proof/sumcheck_rows.h), raw: rows past a column's end are zero; nothing
+// is common to the columns of a row (every column has its own length)
+struct no_row_state {};
+template <class F> struct column_tables {
+  const column_view* views;
+  u64 mid;
+  BZ_HD no_row_state row(u64) const { return {}; }
+  BZ_HD void pair(u32 mle, u64 i, no_row_state, typename F::fe& a, typename F::fe& b) const {
+    const column_view c = views[mle];
+    a = i < c.n ? load_raw<F>(c, i) : F::zero();
+    b = mid + i < c.n ? fsub<F>(load_raw<F>(c, mid + i), a) : fneg<F>(a);
+  }
+};
+
+//--------------------------------------------------------------------------------------------------
+// device kernels
+//--------------------------------------------------------------------------------------------------
+// round 0, round_degree D <= kFixedDegree: k_sumcheck_round_fixed's expansion (no scratch memory);
+// `products`: the multipliers times their terms' conversion constants
+template <class F, u32 D>
+__global__ void __launch_bounds__(kRoundThreads)
+    k_sumcheck_columns_round(typename F::fe* __restrict__ partials,
+                             const column_view* __restrict__ views, u64 mid,
+                             const product_desc<F>* __restrict__ products, u32 num_products,
+                             const u32* __restrict__ terms) {
+  using fe = typename F::fe;
+  __shared__ fe tree[D + 1][kRoundThreads];
+  fe poly[D + 1];
+#pragma unroll
+  for (u32 k = 0; k <= D; ++k) poly[k] = F::zero();
+  const column_tables<F> tables{views, mid};
+  for (u64 i = static_cast<u64>(blockIdx.x) * kRoundThreads + threadIdx.x; i < mid;
+       i += static_cast<u64>(gridDim.x) * kRoundThreads) {
+    accumulate_row_fixed<F, D>(poly, tables, i, products, num_products, terms);
+  }
+  store_partials<F, D>(partials + static_cast<u64>(blockIdx.x) * (kMaxDegree + 1), tree, poly);
+}
+
+// round 0, round_degree 6 .. 8: product lengths at run time
+template <class F>
+__global__ void __launch_bounds__(kRoundThreads)
+    k_sumcheck_columns_generic(typename F::fe* __restrict__ partials,
+                               const column_view* __restrict__ views, u64 mid,
+                               const product_desc<F>* __restrict__ products, u32 num_products,
+                               const u32* __restrict__ terms, u32 degree) {
+  using fe = typename F::fe;
+  __shared__ fe tree[kRoundThreads];
+  fe poly[kMaxDegree + 1];
+  for (u32 k = 0; k <= kMaxDegree; ++k) poly[k] = F::zero();
+  const column_tables<F> tables{views, mid};
+  for (u64 i = static_cast<u64>(blockIdx.x) * kRoundThreads + threadIdx.x; i < mid;
+       i += static_cast<u64>(gridDim.x) * kRoundThreads) {
+    accumulate_row<F>(poly, tables, i, products, num_products, terms);
+  }
+  for (u32 k = 0; k <= degree; ++k) {
+    const fe sum = block_sum<F>(tree, poly[k]);
+    if (threadIdx.x == 0) partials[static_cast<u64>(blockIdx.x) * (kMaxDegree + 1) + k] = sum;
+  }
+}
+
+// r and 1 - r times the conversion constant of integers and of elements
+template <class F> struct fold_factors {
+  typename F::fe r[2], one_minus_r[2];
+};
+// the first fold: out[m * mid + i] = (1 - r) f_m[i] + r f_m[mid + i] in engine form, every i < mid
+template <class F>
+__global__ void __launch_bounds__(256)
+    k_sumcheck_columns_fold(typename F::fe* __restrict__ out, const column_view* __restrict__ views,
+                            u64 mid, u32 num_mles, fold_factors<F> factors) {
+  const u64 id = static_cast<u64>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (id >= mid * num_mles) return;
+  const u64 m = id / mid, i = id % mid;
+  const column_view c = views[m];
+  const bool element = c.nbytes == 32;
+  typename F::fe v = F::zero();
+  if (i < c.n) {
+    v = F::mul(load_raw<F>(c, i), F::select(factors.one_minus_r[0], factors.one_minus_r[1], element));
+  }
+  if (mid + i < c.n) {
+    v = fadd<F>(v, F::mul(F::select(factors.r[0], factors.r[1], element), load_raw<F>(c, mid + i)));
+  }
+  out[id] = v;
+}
+
+template <class F, u32 D>
+void launch_columns_round(hipStream_t stream, u32 blocks, typename F::fe* d_partials,
+                          const column_view* d_views, u64 mid, const product_desc<F>* d_products,
+                          u32 num_products, const u32* d_terms, u32 degree) {
+  if (degree == D) {
+    hipLaunchKernelGGL((k_sumcheck_columns_round<F, D>), dim3(blocks), dim3(kRoundThreads), 0,
+                       stream, d_partials, d_views, mid, d_products, num_products, d_terms);
+    return;
+  }
+  if constexpr (D < kFixedDegree) {
+    launch_columns_round<F, D + 1>(stream, blocks, d_partials, d_views, mid, d_products,
+                                   num_products, d_terms, degree);
+  } else {
+    hipLaunchKernelGGL((k_sumcheck_columns_generic<F>), dim3(blocks), dim3(kRoundThreads), 0,
+                       stream, d_partials, d_views, mid, d_products, num_products, d_terms, degree);
+  }
+}
+
+//--------------------------------------------------------------------------------------------------
+// `upload`: the columns are host memory and the proof runs on a device
+template <class E> class column_source final : public first_round_source<typename E::F> {
+public:
+  using F = typename E::F;
+  using fe = typename F::fe;
+
+  column_source(const sumcheck_column* columns, u32 num_mles, bool upload)
+      : views_(num_mles), upload_(upload) {
+    for (u32 j = 0; j < num_mles; ++j) {
+      const sumcheck_column& c = columns[j];
+      views_[j] = column_view{static_cast<const u8*>(c.data), c.n, c.nbytes,
+                              access_of(c.data, c.nbytes), c.is_signed ? 1u : 0u, 0};
+    }
+  }
+
+  void bind(const product_desc<F>* products, u32 num_products, const u32* terms) override {
+    products_.assign(products, products + num_products);
+    for (product_desc<F>& p : products_) {
+      for (u32 t = 0; t < p.num_terms; ++t) {
+        const column_view& c = views_[terms[p.first_term + t]];
+        p.multiplier = F::mul(p.multiplier, E::conversion(c.nbytes == E::element_bytes));
+      }
+    }
+  }
+
+  size_t device_bytes() const override {
+    size_t bytes = device_arena::padded(sizeof(column_view) * views_.size()) +
+                   device_arena::padded(sizeof(product_desc<F>) * products_.size());
+    if (upload_) {
+      for (const column_view& c : views_) bytes += device_arena::padded(c.n * c.nbytes);
+    }
+    return bytes;
+  }
+
+  void stage(device_arena& arena, hipStream_t stream) override {
+    if (upload_) {
+      for (column_view& c : views_) {
+        const size_t bytes = c.n * c.nbytes;
+        u8* staged = arena.take<u8>(bytes);
+        if (bytes != 0) {
+          BZ_HIP_CHECK(hipMemcpyAsync(staged, c.data, bytes, hipMemcpyHostToDevice, stream));
+        }
+        c.data = staged;
+        c.access = access_of(staged, c.nbytes);
+      }
+    }
+    d_views_ = arena.take<column_view>(views_.size());
+    BZ_HIP_CHECK(hipMemcpyAsync(d_views_, views_.data(), sizeof(column_view) * views_.size(),
+                                hipMemcpyHostToDevice, stream));
+    d_products_ = arena.take<product_desc<F>>(products_.size());
+    BZ_HIP_CHECK(hipMemcpyAsync(d_products_, products_.data(),
+                                sizeof(product_desc<F>) * products_.size(), hipMemcpyHostToDevice,
+                                stream));
+  }
+
+  void round(hipStream_t stream, u32 blocks, fe* partials, u64 mid, const u32* terms,
+             u32 degree) override {
+    launch_columns_round<F, 1>(stream, blocks, partials, d_views_, mid, d_products_,
+                               static_cast<u32>(products_.size()), terms, degree);
+  }
+
+  void fold(hipStream_t stream, fe* out, u64 mid, const fe& r, const fe& one_minus_r) override {
+    const u32 num_mles = static_cast<u32>(views_.size());
+    fold_factors<F> factors;
+    for (int element = 0; element < 2; ++element) {
+      factors.r[element] = F::mul(r, E::conversion(element != 0));
+      factors.one_minus_r[element] = F::mul(one_minus_r, E::conversion(element != 0));
+    }
+    hipLaunchKernelGGL((k_sumcheck_columns_fold<F>), dim3(ceil_div_u32(mid * num_mles, 256)),
+                       dim3(256), 0, stream, out, d_views_, mid, num_mles, factors);
+  }
+
+  void load_host(fe* out, u64 n) const override {
+    for (size_t m = 0; m < views_.size(); ++m) {
+      const column_view& c = views_[m];
+      for (u64 i = 0; i < n; ++i) out[m * n + i] = i < c.n ? load_element<E>(c, i) : F::zero();
+    }
+  }
+
+private:
+  std::vector<column_view> views_;
+  std::vector<product_desc<F>> products_; // multipliers times their terms' conversion constants
+  column_view* d_views_ = nullptr;
+  product_desc<F>* d_products_ = nullptr;
+  bool upload_;
+};
+
+template <class E>
+void prove_columns(api_state& st, void* polynomials, void* evaluation_point, void* mle_evaluations,
+                   const sumcheck_inputs& d, const sumcheck_column* columns, void* callback,
+                   void* context, api_state::device_lease* lease,
+                   const sumcheck_device_tables* device_tables) {
+  column_source<E> source(columns, d.num_mles, st.backend == 2 && device_tables == nullptr);
+  prove<E>(st, static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
+           static_cast<u8*>(mle_evaluations), d, callback, context, lease, device_tables, &source);
+}
+} // namespace
+
+void prove_sumcheck_columns(api_state& st, void* polynomials, void* evaluation_point,
+                            void* mle_evaluations, unsigned field_id, const sumcheck_inputs& d,
+                            const sumcheck_column* columns, void* callback, void* context,
+                            api_state::device_lease* lease,
+                            const sumcheck_device_tables* device_tables) {
+  check_sumcheck_limits(d);
+  for (u32 j = 0; j < d.num_mles; ++j) {
+    BZ_RELEASE_ASSERT(columns[j].n <= d.n, "a sumcheck column is longer than n");
+  }
+  if (field_id == 0) {
+    prove_columns<scalar25519_elements>(st, polynomials, evaluation_point, mle_evaluations, d,
+                                        columns, callback, context, lease, device_tables);
+  } else if (field_id == 1) {
+    prove_columns<grumpkin_elements>(st, polynomials, evaluation_point, mle_evaluations, d, columns,
+                                     callback, context, lease, device_tables);
+  } else {
+    BZ_RELEASE_ASSERT(false, "unsupported field id");
+  }
+}
+} // namespace bz::proof

@@ -294,6 +294,42 @@ void bzamd_prove_sumcheck_device(void* polynomials, void* evaluation_point, void
                                  unsigned field_id, const struct sumcheck_descriptor* descriptor,
                                  void* transcript_callback, void* transcript_context, void* stream);
 
+/* Sumcheck over typed columns: the MLEs are described by the descriptors the MSM entry points
+ * take, so a service proves over the columns it has just committed, as they are.  MLE j has
+ * mles[j].n <= n rows (longer aborts); rows mles[j].n .. n - 1 are zero (n = 0 with data = NULL is
+ * a zero column).  element_nbytes 1 .. 31: little-endian integers, two's complement when
+ * is_signed (a negative v is the field's p - |v|); for SXT_FIELD_GRUMPKIN the library converts the
+ * integer into Montgomery form.  element_nbytes 32: field elements in the representation
+ * sxt_prove_sumcheck takes for the field.  Descriptors are validated by the MSM's rule
+ * (element_nbytes in [1, 32], signed only up to 16 bytes).  Everything else -- outputs, product
+ * table, limits, callback -- is as in bzamd_prove_sumcheck, and the outputs are the bytes
+ * sxt_prove_sumcheck writes for the columns widened to 32 bytes and padded with zero rows to n. */
+struct bzamd_sumcheck_columns {
+  const struct sxt_sequence_descriptor* mles; /* num_mles descriptors, one per MLE */
+  const void* product_table;                  /* as sumcheck_descriptor */
+  const unsigned* product_terms;
+  unsigned n, num_mles, num_products, num_product_terms, round_degree;
+};
+/* mles[j].data on the HOST; blocking, cpu and gpu backends.  The gpu backend uploads the columns
+ * at their own width. */
+void bzamd_prove_sumcheck_columns(void* polynomials, void* evaluation_point, void* mle_evaluations,
+                                  unsigned field_id, const struct bzamd_sumcheck_columns* columns,
+                                  void* transcript_callback, void* transcript_context);
+/* mles[j].data are DEVICE pointers on the current HIP device; everything else, the descriptors
+ * included, is HOST.  The rules of bzamd_prove_sumcheck_device hold: gpu backend only, kernels on
+ * `stream`, the columns read in stream order and never written, no device of the backend held
+ * (the callback may call back into the library), mle_evaluations may be NULL.  Round 0 and the
+ * first fold read the columns where they lie; the call's device memory holds the folded tables
+ * only (27 bytes per padded row and MLE). */
+void bzamd_prove_sumcheck_device_columns(void* polynomials, void* evaluation_point,
+                                         void* mle_evaluations, unsigned field_id,
+                                         const struct bzamd_sumcheck_columns* columns,
+                                         void* transcript_callback, void* transcript_context,
+                                         void* stream);
+/* Device memory the latest sumcheck call of the process on the gpu backend allocated, in bytes:
+ * working tables, staged operands and round buffers (0 before the first one). */
+uint64_t bzamd_sumcheck_device_bytes(void);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

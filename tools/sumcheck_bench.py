@@ -4,10 +4,16 @@ benchmark/sumcheck/benchmark.m.cc (degree x num_products random MLEs of n rows, 
 length `degree`, a hash transcript), for both fields of the ABI.
 
     python tools/sumcheck_bench.py <n> <degree> <num_products> <num_samples> [--fields 0,1]
+                                   [--column-bytes 1|2|4|8]
 
 Timed, with a device synchronise inside the clock, after one untimed call:
   host    sxt_prove_sumcheck: the tables start in host memory (their upload is part of the call);
   device  bzamd_prove_sumcheck_device: the tables are resident in HBM before the clock starts.
+With --column-bytes W the MLEs are signed integers of W bytes, the tables of the two legs above are
+those values widened to 32 bytes, and two more legs run beside them on resident operands:
+  columns     bzamd_prove_sumcheck_device_columns on the W-byte columns;
+  columns32   the same entry point on the widened tables, as num_mles columns of 32 bytes.
+Both must return the device leg's bytes; `device_bytes` is the device memory each form allocated.
 The transcript callback is Python (one ctypes call and one SHA-256 per round); its cost is timed
 alone and printed beside the two (`callback_ms`) -- it is inside both figures and is not kernel time.
 BLITZAR_AMD_LIB selects the library (A/B against another build in one session); a library without
@@ -38,6 +44,35 @@ def random_elements(rng, field_id, count):
     out = rng.integers(0, 256, (count, 32), dtype=np.uint8)
     out[:, 31] &= TOP_BYTE_MASK[field_id]
     return out
+
+
+def integer_columns(rng, width, n, num_mles):
+    """num_mles columns of n signed integers of `width` bytes, as int64 and as their own bytes"""
+    bits = 8 * width
+    values = rng.integers(-(1 << (bits - 1)), (1 << (bits - 1)) - 1, (num_mles, n), dtype=np.int64,
+                          endpoint=True)
+    raw = np.ascontiguousarray(values.view(np.uint8).reshape(num_mles, n, 8)[:, :, :width])
+    return values, raw
+
+
+def widen(field_id, values):
+    """int64 [..] -> the field elements v mod p in the caller's representation, uint8 [.., 32]"""
+    p = MODULUS[field_id]
+    if field_id == 0:
+        # plain little-endian integers: |v| in limb 0, and p - |v| for v < 0 (p's limb 0 may borrow
+        # from limb 1, which is not zero)
+        limbs = np.zeros(values.shape + (4,), np.uint64)
+        negative = values < 0
+        magnitude = np.where(negative, -values, values).astype(np.uint64)
+        p_limbs = [np.uint64((p >> (64 * k)) & (2**64 - 1)) for k in range(4)]
+        limbs[..., 0] = np.where(negative, p_limbs[0] - magnitude, magnitude)
+        limbs[..., 1] = np.where(negative, p_limbs[1] - (magnitude > p_limbs[0]).astype(np.uint64), 0)
+        limbs[..., 2] = np.where(negative, p_limbs[2], 0)
+        limbs[..., 3] = np.where(negative, p_limbs[3], 0)
+        return limbs.view(np.uint8).reshape(values.shape + (32,))
+    r = (1 << 256) % p  # Montgomery form; in Python integers
+    flat = b"".join((int(v) * r % p).to_bytes(32, "little") for v in values.reshape(-1).tolist())
+    return np.frombuffer(flat, np.uint8).reshape(values.shape + (32,)).copy()
 
 
 def hash_callback(field_id):
@@ -74,6 +109,7 @@ def main():
     ap.add_argument("num_products", type=int)
     ap.add_argument("num_samples", type=int)
     ap.add_argument("--fields", default="0,1")
+    ap.add_argument("--column-bytes", type=int, choices=[1, 2, 4, 8], default=None)
     args = ap.parse_args()
     lib = api.load()
     assert lib.bzamd_device_count() > 0, "sumcheck_bench needs a GPU"
@@ -87,9 +123,17 @@ def main():
     rec = {"n": n, "degree": degree, "num_products": num_products, "num_mles": num_mles,
            "rounds": rounds, "num_samples": args.num_samples, "library": api.LIB_PATH,
            "table_bytes": 32 * n * num_mles, "fields": {}}
+    if args.column_bytes is not None:
+        assert has_device_form and hasattr(lib, "bzamd_prove_sumcheck_device_columns"), \
+            "--column-bytes needs a library with the columns form"
+        rec["column_bytes"] = args.column_bytes
     for field_id in (int(x) for x in args.fields.split(",")):
         rng = np.random.default_rng(1 + field_id)
-        mles = random_elements(rng, field_id, n * num_mles).reshape(num_mles, n, 32)
+        if args.column_bytes is None:
+            mles = random_elements(rng, field_id, n * num_mles).reshape(num_mles, n, 32)
+        else:
+            values, raw = integer_columns(rng, args.column_bytes, n, num_mles)
+            mles = widen(field_id, values)
         stride = api.SUMCHECK_PRODUCT_STRIDE[field_id]
         table = np.zeros((num_products, stride), np.uint8)
         table[:, :32] = random_elements(rng, field_id, num_products)
@@ -111,12 +155,32 @@ def main():
                                                           table, terms, n, degree, cb)
 
             result["device"] = summary(samples_ms(device, args.num_samples))
+            result["device_bytes"] = {"device": int(lib.bzamd_sumcheck_device_bytes())} \
+                if hasattr(lib, "bzamd_sumcheck_device_bytes") else {}
             result["device_saves_upload_bytes"] = rec["table_bytes"]
             same = all(np.array_equal(a, b) for a, b in zip(out["host"], out["device"][:2]))
             result["device_equals_host"] = bool(same)
             assert same, "the device form disagrees with sxt_prove_sumcheck"
         else:
             result["device"] = "absent"
+        if args.column_bytes is not None:
+            d_raw = torch.from_numpy(raw).to(dev)
+            torch.cuda.synchronize()
+            width = args.column_bytes
+            legs = {"columns": [(d_raw.data_ptr() + j * n * width, n, width, True)
+                                for j in range(num_mles)],
+                    "columns32": [(d_mles.data_ptr() + j * n * 32, n, 32, False)
+                                  for j in range(num_mles)]}
+            for leg, descriptors in legs.items():
+                def columns():
+                    out[leg] = api.prove_sumcheck_device_columns(field_id, descriptors, table, terms,
+                                                                 n, degree, cb)
+
+                result[leg] = summary(samples_ms(columns, args.num_samples))
+                result["device_bytes"][leg] = int(lib.bzamd_sumcheck_device_bytes())
+                same = all(np.array_equal(a, b) for a, b in zip(out[leg], out["device"]))
+                assert same, f"the {leg} form disagrees with bzamd_prove_sumcheck_device"
+            result["columns_equal_device"] = True
         # the Python transcript alone: `rounds` calls through ctypes, as the prover makes them
         c_cb = api.SUMCHECK_CALLBACK(cb)
         poly = np.ascontiguousarray(out["host"][0][0])
