@@ -178,6 +178,18 @@ def load():
     lib.bzamd_set_shard_min_bytes.restype = None
     lib.bzamd_accumulate_form.restype = ctypes.c_int
     lib.bzamd_sumcheck_device_bytes.restype = ctypes.c_uint64
+    lib.bzamd_sumcheck_transcript_begin.argtypes = [vp, u64, u64]
+    lib.bzamd_sumcheck_transcript_begin.restype = None
+    lib.bzamd_sumcheck_transcript_round.argtypes = [vp, vp, vp, cu]
+    lib.bzamd_sumcheck_transcript_round.restype = None
+    lib.bzamd_prove_sumcheck_transcript.argtypes = [vp, vp, vp, vp, cu, vp]
+    lib.bzamd_prove_sumcheck_transcript.restype = None
+    lib.bzamd_sumcheck_transcript_workspace_bytes.argtypes = [cu, vp]
+    lib.bzamd_sumcheck_transcript_workspace_bytes.restype = u64
+    lib.bzamd_prove_sumcheck_transcript_device.argtypes = [vp, vp, vp, vp, cu, vp, vp, u64, vp]
+    lib.bzamd_prove_sumcheck_transcript_device.restype = None
+    lib.bzamd_verify_sumcheck.argtypes = [vp, vp, vp, cu, vp, cu, cu]
+    lib.bzamd_verify_sumcheck.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -355,7 +367,7 @@ SUMCHECK_PRODUCT_STRIDE = {0: 36, 1: 40}  # std::pair<FIELD, unsigned> of the re
 
 
 def _sumcheck_call(symbol, field_id, mles_ptr, num_mles, product_table, product_terms, n,
-                   round_degree, callback, with_evaluations, stream=None):
+                   round_degree, callback, with_evaluations, stream=None, context=None):
     table = np.ascontiguousarray(product_table, dtype=np.uint8)
     terms = np.ascontiguousarray(product_terms, dtype=np.uint32)
     num_variables = max((int(n) - 1).bit_length(), 1)
@@ -364,51 +376,142 @@ def _sumcheck_call(symbol, field_id, mles_ptr, num_mles, product_table, product_
     d = sumcheck_descriptor(mles_ptr, table.ctypes.data, terms.ctypes.data, n, num_mles,
                             table.size // SUMCHECK_PRODUCT_STRIDE[field_id], terms.size,
                             round_degree)
-    cb = SUMCHECK_CALLBACK(callback)
+    cb = callback if isinstance(callback, SUMCHECK_CALLBACK) else SUMCHECK_CALLBACK(callback)
     vp = ctypes.c_void_p
     fn = getattr(load(), symbol)
     fn.restype = None
     tail = [ctypes.c_uint, ctypes.POINTER(sumcheck_descriptor), SUMCHECK_CALLBACK, vp]
     if not with_evaluations:
         fn.argtypes = [vp, vp] + tail
-        fn(_ptr(polys), _ptr(point), field_id, ctypes.byref(d), cb, None)
+        fn(_ptr(polys), _ptr(point), field_id, ctypes.byref(d), cb, context)
         return polys, point
     evaluations = np.zeros((num_mles, 32), dtype=np.uint8)
     if symbol == "bzamd_prove_sumcheck_device":
         fn.argtypes = [vp, vp, vp] + tail + [vp]
-        fn(_ptr(polys), _ptr(point), _ptr(evaluations), field_id, ctypes.byref(d), cb, None, stream)
+        fn(_ptr(polys), _ptr(point), _ptr(evaluations), field_id, ctypes.byref(d), cb, context,
+           stream)
     else:
         fn.argtypes = [vp, vp, vp] + tail
-        fn(_ptr(polys), _ptr(point), _ptr(evaluations), field_id, ctypes.byref(d), cb, None)
+        fn(_ptr(polys), _ptr(point), _ptr(evaluations), field_id, ctypes.byref(d), cb, context)
     return polys, point, evaluations
 
 
-def prove_sumcheck(field_id, mles, product_table, product_terms, n, round_degree, callback):
+def prove_sumcheck(field_id, mles, product_table, product_terms, n, round_degree, callback,
+                   context=None):
     """sxt_prove_sumcheck.  mles: uint8 [num_mles, n, 32]; product_table: raw bytes of
     num_products x {32-byte multiplier; unsigned length}; callback(r_ptr, ctx, poly_ptr, length).
     -> (polynomials [num_variables, round_degree + 1, 32], evaluation_point [num_variables, 32])"""
     m = np.ascontiguousarray(mles, dtype=np.uint8)
     return _sumcheck_call("sxt_prove_sumcheck", field_id, m.ctypes.data, m.shape[0], product_table,
-                          product_terms, n, round_degree, callback, False)
+                          product_terms, n, round_degree, callback, False, context=context)
 
 
 def prove_sumcheck_with_evaluations(field_id, mles, product_table, product_terms, n, round_degree,
-                                    callback):
+                                    callback, context=None):
     """bzamd_prove_sumcheck: prove_sumcheck plus mle_evaluations [num_mles, 32], the value of every
     MLE at the evaluation point -> (polynomials, evaluation_point, mle_evaluations)"""
     m = np.ascontiguousarray(mles, dtype=np.uint8)
     return _sumcheck_call("bzamd_prove_sumcheck", field_id, m.ctypes.data, m.shape[0],
-                          product_table, product_terms, n, round_degree, callback, True)
+                          product_table, product_terms, n, round_degree, callback, True,
+                          context=context)
 
 
 def prove_sumcheck_device(field_id, mles_device_ptr, num_mles, product_table, product_terms, n,
-                          round_degree, callback, stream=None):
+                          round_degree, callback, stream=None, context=None):
     """bzamd_prove_sumcheck_device: the tables ([num_mles, n, 32] bytes) are device memory of the
     current device at `mles_device_ptr`, `stream` a hipStream_t as an integer (None: the default
     stream); everything else on the host -> (polynomials, evaluation_point, mle_evaluations)"""
     return _sumcheck_call("bzamd_prove_sumcheck_device", field_id, int(mles_device_ptr), num_mles,
                           product_table, product_terms, n, round_degree, callback, True,
-                          None if stream is None else ctypes.c_void_p(int(stream)))
+                          None if stream is None else ctypes.c_void_p(int(stream)), context=context)
+
+
+#--------------------------------------------------------------------------------------------------
+# sumcheck with the library's own transcript (the reference's reference_transcript)
+#--------------------------------------------------------------------------------------------------
+class bzamd_sumcheck_transcript_context(ctypes.Structure):
+    _fields_ = [("transcript", ctypes.c_void_p), ("field_id", ctypes.c_uint)]
+
+
+def __getattr__(name):
+    # SUMCHECK_TRANSCRIPT_ROUND: bzamd_sumcheck_transcript_round as a SUMCHECK_CALLBACK, for the
+    # `callback` of the entry points above with a bzamd_sumcheck_transcript_context (by reference)
+    # as their `context`; made on first use, the library is not loaded on import
+    if name == "SUMCHECK_TRANSCRIPT_ROUND":
+        cb = ctypes.cast(load().bzamd_sumcheck_transcript_round, SUMCHECK_CALLBACK)
+        globals()[name] = cb
+        return cb
+    raise AttributeError(name)
+
+
+def sumcheck_transcript_begin(transcript, num_variables, round_degree):
+    """bzamd_sumcheck_transcript_begin, in place on a uint8 [203] array"""
+    assert transcript.dtype == np.uint8 and transcript.size == 203
+    load().bzamd_sumcheck_transcript_begin(_ptr(transcript), num_variables, round_degree)
+
+
+def _transcript_descriptor(field_id, mles_ptr, num_mles, product_table, product_terms, n,
+                           round_degree):
+    table = np.ascontiguousarray(product_table, dtype=np.uint8)
+    terms = np.ascontiguousarray(product_terms, dtype=np.uint32)
+    d = sumcheck_descriptor(mles_ptr, table.ctypes.data, terms.ctypes.data, n, num_mles,
+                            table.size // SUMCHECK_PRODUCT_STRIDE[field_id], terms.size,
+                            round_degree)
+    return d, (table, terms)
+
+
+def prove_sumcheck_transcript(field_id, mles, product_table, product_terms, n, round_degree,
+                              transcript, with_evaluations=True):
+    """bzamd_prove_sumcheck_transcript (host operands, either backend)
+    -> (polynomials, evaluation_point, mle_evaluations or None, transcript after)"""
+    m = np.ascontiguousarray(mles, dtype=np.uint8)
+    d, _keep = _transcript_descriptor(field_id, m.ctypes.data, m.shape[0], product_table,
+                                      product_terms, n, round_degree)
+    num_variables = max((int(n) - 1).bit_length(), 1)
+    polys = np.zeros((num_variables, round_degree + 1, 32), dtype=np.uint8)
+    point = np.zeros((num_variables, 32), dtype=np.uint8)
+    evaluations = np.zeros((m.shape[0], 32), dtype=np.uint8) if with_evaluations else None
+    t = np.ascontiguousarray(transcript, dtype=np.uint8).copy()
+    load().bzamd_prove_sumcheck_transcript(_ptr(polys), _ptr(point), _ptr(evaluations), _ptr(t),
+                                           field_id, ctypes.byref(d))
+    return polys, point, evaluations, t
+
+
+def sumcheck_transcript_workspace_bytes(field_id, n, num_mles, num_products, num_product_terms,
+                                        round_degree):
+    d = sumcheck_descriptor(None, None, None, n, num_mles, num_products, num_product_terms,
+                            round_degree)
+    return load().bzamd_sumcheck_transcript_workspace_bytes(field_id, ctypes.byref(d))
+
+
+def prove_sumcheck_transcript_device(field_id, mles_device_ptr, num_mles, product_table,
+                                     product_terms, n, round_degree, polynomials_ptr,
+                                     evaluation_point_ptr, mle_evaluations_ptr, transcript_ptr,
+                                     workspace_ptr, workspace_bytes, stream=None):
+    """bzamd_prove_sumcheck_transcript_device: enqueue only.  Every *_ptr is memory of the current
+    device as an integer (torch: tensor.data_ptr()), mle_evaluations_ptr may be None; `stream` a
+    hipStream_t as an integer (None: the default stream).  Results are in the caller's device
+    memory once the stream has run."""
+    d, _keep = _transcript_descriptor(field_id, int(mles_device_ptr), num_mles, product_table,
+                                      product_terms, n, round_degree)
+    load().bzamd_prove_sumcheck_transcript_device(
+        int(polynomials_ptr), int(evaluation_point_ptr),
+        None if mle_evaluations_ptr is None else int(mle_evaluations_ptr), int(transcript_ptr),
+        field_id, ctypes.byref(d), int(workspace_ptr), workspace_bytes,
+        None if stream is None else ctypes.c_void_p(int(stream)))
+
+
+def verify_sumcheck(field_id, claimed_sum, round_polynomials, transcript):
+    """bzamd_verify_sumcheck.  round_polynomials: uint8 [num_variables, round_degree + 1, 32]
+    -> (ok, expected_sum after, evaluation_point, transcript after)"""
+    polys = np.ascontiguousarray(round_polynomials, dtype=np.uint8)
+    num_variables, length = polys.shape[0], polys.shape[1]
+    expected = np.ascontiguousarray(claimed_sum, dtype=np.uint8).copy()
+    point = np.zeros((num_variables, 32), dtype=np.uint8)
+    t = np.ascontiguousarray(transcript, dtype=np.uint8).copy()
+    ok = load().bzamd_verify_sumcheck(_ptr(expected), _ptr(point), _ptr(t), field_id, _ptr(polys),
+                                      num_variables, length - 1)
+    return bool(ok), expected, point, t
 
 
 class bzamd_sumcheck_columns(ctypes.Structure):

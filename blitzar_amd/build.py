@@ -34,6 +34,7 @@ SOURCES = [
     "proof/inner_product.hip",
     "proof/sumcheck.hip",
     "proof/sumcheck_columns.hip",
+    "proof/sumcheck_transcript.hip",
     "api/capi.hip",
 ]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-I" + ROOT,

@@ -25,6 +25,7 @@
 #include "blitzar_amd/csrc/fixed/handle.h"
 #include "blitzar_amd/csrc/proof/inner_product.h"
 #include "blitzar_amd/csrc/proof/sumcheck.h"
+#include "blitzar_amd/csrc/proof/sumcheck_transcript.h"
 #include "blitzar_amd/csrc/proof/transcript.h"
 #include "include/blitzar_amd.h"
 
@@ -1712,6 +1713,90 @@ void bzamd_prove_sumcheck_device_columns(void* polynomials, void* evaluation_poi
 }
 
 uint64_t bzamd_sumcheck_device_bytes(void) { return proof::g_sumcheck_arena_bytes.load(); }
+
+// sumcheck with the library's own transcript (proof/sumcheck_transcript.hip)
+void bzamd_sumcheck_transcript_begin(struct sxt_transcript* transcript, uint64_t num_variables,
+                                     uint64_t round_degree) {
+  BZ_RELEASE_ASSERT(transcript != nullptr, "transcript must not be null");
+  proof::sumcheck_transcript_begin(transcript, num_variables, round_degree);
+}
+
+void bzamd_sumcheck_transcript_round(void* r, void* context, const void* polynomial,
+                                     unsigned length) {
+  BZ_RELEASE_ASSERT(r != nullptr && context != nullptr && polynomial != nullptr,
+                    "null argument to `bzamd_sumcheck_transcript_round`");
+  const auto* c = static_cast<const bzamd_sumcheck_transcript_context*>(context);
+  BZ_RELEASE_ASSERT(c->transcript != nullptr, "transcript must not be null");
+  proof::sumcheck_transcript_round(r, c->transcript, c->field_id, polynomial, length);
+}
+
+namespace {
+proof::sumcheck_inputs transcript_form_inputs(const char* name, const void* polynomials,
+                                              const void* evaluation_point, const void* transcript,
+                                              const struct sumcheck_descriptor* descriptor) {
+  if (polynomials == nullptr || evaluation_point == nullptr || descriptor == nullptr ||
+      transcript == nullptr) {
+    std::fprintf(stderr, "blitzar_amd: null argument to `%s`\n", name);
+    std::abort();
+  }
+  BZ_RELEASE_ASSERT(descriptor->mles != nullptr && descriptor->product_table != nullptr &&
+                        descriptor->product_terms != nullptr,
+                    "null table in the sumcheck descriptor");
+  return proof::sumcheck_inputs{descriptor->mles,         descriptor->product_table,
+                                descriptor->product_terms, descriptor->n,
+                                descriptor->num_mles,      descriptor->num_products,
+                                descriptor->num_product_terms, descriptor->round_degree};
+}
+} // namespace
+
+void bzamd_prove_sumcheck_transcript(void* polynomials, void* evaluation_point,
+                                     void* mle_evaluations, struct sxt_transcript* transcript,
+                                     unsigned field_id, const struct sumcheck_descriptor* descriptor) {
+  const proof::sumcheck_inputs in = transcript_form_inputs(
+      "bzamd_prove_sumcheck_transcript", polynomials, evaluation_point, transcript, descriptor);
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::prove_sumcheck_transcript(st, polynomials, evaluation_point, mle_evaluations, transcript,
+                                   field_id, in);
+}
+
+uint64_t bzamd_sumcheck_transcript_workspace_bytes(unsigned field_id,
+                                                   const struct sumcheck_descriptor* descriptor) {
+  BZ_RELEASE_ASSERT(descriptor != nullptr, "descriptor must not be null");
+  const proof::sumcheck_inputs in{nullptr, nullptr, nullptr, descriptor->n, descriptor->num_mles,
+                                  descriptor->num_products, descriptor->num_product_terms,
+                                  descriptor->round_degree};
+  return proof::sumcheck_transcript_workspace_bytes(field_id, in);
+}
+
+void bzamd_prove_sumcheck_transcript_device(void* polynomials, void* evaluation_point,
+                                            void* mle_evaluations, void* transcript,
+                                            unsigned field_id,
+                                            const struct sumcheck_descriptor* descriptor,
+                                            void* workspace, uint64_t workspace_bytes, void* stream) {
+  const proof::sumcheck_inputs in =
+      transcript_form_inputs("bzamd_prove_sumcheck_transcript_device", polynomials,
+                             evaluation_point, transcript, descriptor);
+  // the current device, the caller's stream and workspace: none of the backend's per-device state
+  // is touched, so no lease is taken
+  BZ_RELEASE_ASSERT(state().backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
+  proof::prove_sumcheck_transcript_device(polynomials, evaluation_point, mle_evaluations, transcript,
+                                          field_id, in, workspace, workspace_bytes,
+                                          static_cast<hipStream_t>(stream));
+}
+
+int bzamd_verify_sumcheck(void* expected_sum, void* evaluation_point,
+                          struct sxt_transcript* transcript, unsigned field_id,
+                          const void* round_polynomials, unsigned num_variables,
+                          unsigned round_degree) {
+  BZ_RELEASE_ASSERT(expected_sum != nullptr && evaluation_point != nullptr &&
+                        transcript != nullptr && round_polynomials != nullptr,
+                    "null argument to `bzamd_verify_sumcheck`");
+  return proof::verify_sumcheck(expected_sum, evaluation_point, transcript, field_id,
+                                round_polynomials, num_variables, round_degree)
+             ? 1
+             : 0;
+}
 
 //--------------------------------------------------------------------------------------------------
 // extensions (include/blitzar_amd.h)

@@ -158,6 +158,31 @@ void host_round(typename F::fe* poly, const typename F::fe* mles, u64 n, u64 mid
 
 } // namespace
 
+// the load and round kernels for the other provers over engine-form tables
+// (proof/sumcheck_transcript.hip)
+template <class E>
+void launch_sumcheck_load(hipStream_t stream, typename E::F::fe* out, const u8* elements, u64 count) {
+  hipLaunchKernelGGL((k_sumcheck_load<E>), dim3(ceil_div_u32(count, 256)), dim3(256), 0, stream, out,
+                     elements, count);
+}
+template void launch_sumcheck_load<scalar25519_elements>(hipStream_t, scalar25_field::fe*, const u8*, u64);
+template void launch_sumcheck_load<grumpkin_elements>(hipStream_t, grumpkin_fq29::fe*, const u8*, u64);
+template <class F>
+void launch_sumcheck_round(hipStream_t stream, u32 blocks, typename F::fe* partials,
+                           const typename F::fe* mles, u64 n, u64 mid,
+                           const product_desc<F>* products, u32 num_products, const u32* terms,
+                           u32 degree) {
+  launch_round<F, 1>(stream, blocks, partials, mles, n, mid, products, num_products, terms, degree);
+}
+template void launch_sumcheck_round<scalar25_field>(hipStream_t, u32, scalar25_field::fe*,
+                                                    const scalar25_field::fe*, u64, u64,
+                                                    const product_desc<scalar25_field>*, u32,
+                                                    const u32*, u32);
+template void launch_sumcheck_round<grumpkin_fq29>(hipStream_t, u32, grumpkin_fq29::fe*,
+                                                   const grumpkin_fq29::fe*, u64, u64,
+                                                   const product_desc<grumpkin_fq29>*, u32,
+                                                   const u32*, u32);
+
 template <class E>
 void prove(api_state& st, u8* polynomials, u8* evaluation_point, u8* mle_evaluations,
            const sumcheck_inputs& d, void* callback, void* context, api_state::device_lease* lease,
@@ -172,22 +197,7 @@ void prove(api_state& st, u8* polynomials, u8* evaluation_point, u8* mle_evaluat
   while ((u64{1} << num_variables) < n) ++num_variables;
   if (num_variables == 0) num_variables = 1;
 
-  // products in engine form
-  std::vector<product_desc<F>> products(d.num_products);
-  u32 first = 0;
-  for (u32 p = 0; p < d.num_products; ++p) {
-    const u8* entry = static_cast<const u8*>(d.product_table) + static_cast<size_t>(E::product_stride) * p;
-    u32 num_terms;
-    std::memcpy(&num_terms, entry + E::element_bytes, sizeof(num_terms));
-    BZ_RELEASE_ASSERT(num_terms >= 1 && num_terms <= degree,
-                      "a sumcheck product must have between 1 and round_degree terms");
-    products[p] = product_desc<F>{E::load(entry), first, num_terms};
-    first += num_terms;
-  }
-  BZ_RELEASE_ASSERT(first == d.num_product_terms, "num_product_terms does not match the product table");
-  for (u32 t = 0; t < d.num_product_terms; ++t) {
-    BZ_RELEASE_ASSERT(d.product_terms[t] < d.num_mles, "product term refers to a missing MLE");
-  }
+  const std::vector<product_desc<F>> products = engine_products<E>(d);
 
   const bool on_device = st.backend == 2;
   const u64 total = n * d.num_mles;

@@ -5,6 +5,7 @@
 #pragma once
 
 #include <cstring>
+#include <vector>
 
 #include "blitzar_amd/csrc/field/mont29.h"
 #include "blitzar_amd/csrc/proof/scalar25.h"
@@ -77,6 +78,27 @@ template <class F> struct product_desc {
   typename F::fe multiplier;
   u32 first_term, num_terms;
 };
+
+// the descriptor's products in engine form, checked against round_degree and num_mles
+template <class E> std::vector<product_desc<typename E::F>> engine_products(const sumcheck_inputs& d) {
+  using F = typename E::F;
+  std::vector<product_desc<F>> products(d.num_products);
+  u32 first = 0;
+  for (u32 p = 0; p < d.num_products; ++p) {
+    const u8* entry = static_cast<const u8*>(d.product_table) + static_cast<size_t>(E::product_stride) * p;
+    u32 num_terms;
+    std::memcpy(&num_terms, entry + E::element_bytes, sizeof(num_terms));
+    BZ_RELEASE_ASSERT(num_terms >= 1 && num_terms <= d.round_degree,
+                      "a sumcheck product must have between 1 and round_degree terms");
+    products[p] = product_desc<F>{E::load(entry), first, num_terms};
+    first += num_terms;
+  }
+  BZ_RELEASE_ASSERT(first == d.num_product_terms, "num_product_terms does not match the product table");
+  for (u32 t = 0; t < d.num_product_terms; ++t) {
+    BZ_RELEASE_ASSERT(d.product_terms[t] < d.num_mles, "product term refers to a missing MLE");
+  }
+  return products;
+}
 
 // `Tables` of a round: pair(mle, i, row(i), a, b) yields a = f_mle[i] and b = f_mle[mid + i] - a
 // (rows without a partner: b = -a) of the round's `mid`; row(i) is whatever is worth working out
@@ -260,4 +282,13 @@ void prove(api_state& st, u8* polynomials, u8* evaluation_point, u8* mle_evaluat
            const sumcheck_device_tables* device_tables, first_round_source<typename E::F>* source);
 // the limits every entry point shares
 void check_sumcheck_limits(const sumcheck_inputs& d);
+// kernels of proof/sumcheck.hip, enqueued on `stream`: out[i] = E::load(elements + 32 i), and the
+// round kernel for `degree` (partials[block][k], `blocks` workgroups)
+template <class E>
+void launch_sumcheck_load(hipStream_t stream, typename E::F::fe* out, const u8* elements, u64 count);
+template <class F>
+void launch_sumcheck_round(hipStream_t stream, u32 blocks, typename F::fe* partials,
+                           const typename F::fe* mles, u64 n, u64 mid,
+                           const product_desc<F>* products, u32 num_products, const u32* terms,
+                           u32 degree);
 } // namespace bz::proof

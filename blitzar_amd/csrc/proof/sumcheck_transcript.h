@@ -1,0 +1,36 @@
+// Sumcheck with the library's own transcript (proof/sumcheck_transcript.hip): the reference's
+// prfsk::reference_transcript<T> (sxt/proof/sumcheck/reference_transcript.h) over the caller's
+// 203-byte Merlin state, as a callback for the existing entry points, inside a prover that needs
+// no callback -- on the GPU backend one that never returns to the host between rounds -- and the
+// matching verifier (prfsk::verify_sumcheck_no_evaluation, sxt/proof/sumcheck/verification.h).
+#pragma once
+
+#include "blitzar_amd/csrc/proof/sumcheck.h"
+
+namespace bz::proof {
+// reference_transcript::init on the caller's transcript
+void sumcheck_transcript_begin(void* transcript, u64 num_variables, u64 round_degree);
+// reference_transcript::round_challenge: r (32 bytes, the caller's representation) from the round
+// polynomial of `length` elements
+void sumcheck_transcript_round(void* r, void* transcript, unsigned field_id, const void* polynomial,
+                               unsigned length);
+
+// bzamd_prove_sumcheck_transcript: host operands, blocking, st.backend; GPU backend: on devices[0],
+// whose lease the caller holds
+void prove_sumcheck_transcript(api_state& st, void* polynomials, void* evaluation_point,
+                               void* mle_evaluations, void* transcript, unsigned field_id,
+                               const sumcheck_inputs& inputs);
+
+// bzamd_sumcheck_transcript_workspace_bytes / bzamd_prove_sumcheck_transcript_device: everything
+// but the descriptor, the product table and the terms is memory of the current device; the call
+// only enqueues on `stream`
+u64 sumcheck_transcript_workspace_bytes(unsigned field_id, const sumcheck_inputs& inputs);
+void prove_sumcheck_transcript_device(void* polynomials, void* evaluation_point,
+                                      void* mle_evaluations, void* transcript, unsigned field_id,
+                                      const sumcheck_inputs& inputs, void* workspace,
+                                      u64 workspace_bytes, hipStream_t stream);
+
+// bzamd_verify_sumcheck (host arithmetic only)
+bool verify_sumcheck(void* expected_sum, void* evaluation_point, void* transcript, unsigned field_id,
+                     const void* round_polynomials, unsigned num_variables, unsigned round_degree);
+} // namespace bz::proof

@@ -1,0 +1,537 @@
+// Sumcheck with the library's own transcript: prfsk::reference_transcript<T>
+// (sxt/proof/sumcheck/reference_transcript.h) over the caller's 203-byte Merlin state.
+//
+//   init:   append_message("domain-sep", "sumcheck proof v1"), append_message("n", u64 v),
+//           append_message("k", u64 round_degree)
+//   round:  append_message("P", the round polynomial's (D + 1) 32 bytes as written to the caller),
+//           challenge_bytes("R", 32) = x, and r from x by field (prft::challenge_value,
+//           sxt/proof/transcript/transcript_utility.cc):
+//             curve25519 scalars: the integer x mod l (s25o::reduce32)
+//             Grumpkin:           fgkb::to_bytes_le applied to x read as four limbs, i.e. the integer
+//                                 x / 2^256 mod p, canonical -- and THOSE bytes are then the element
+//                                 (Montgomery limbs), so the challenge's value is x / 2^512.  The
+//                                 double interpretation is the reference's; the bytes are the contract.
+//
+// On the host this is a callback for the existing entry points (sumcheck_transcript_round) and the
+// verifier.  On the device the prover never returns to the host between rounds:
+//   k_sumcheck_load, then per round while more than kTailRows pairs are left (or down to the last
+//   round for round degrees 6 .. 8): the round kernel of proof/sumcheck.hip, k_sumcheck_challenge
+//   (adds the workgroups' partials, stores the polynomial, runs the transcript step in LDS, leaves
+//   r and 1 - r in a workspace slot), k_sumcheck_fold_slot; then k_sumcheck_tail runs every
+//   remaining round in one workgroup.
+// Kernel launches of a proof of v variables (c: the rounds before the tail):
+//   round degree <= 5:  c = max(v - 1 - log2(kTailRows), 0),  launches = 1 + 3 c + 1
+//   round degree 6..8:  c = v,  launches = 1 + 3 v, less the last fold when mle_evaluations is NULL
+// The Merlin logic is proof/transcript.h over wave_sponge: wavefront 0 of the workgroup runs it in
+// lockstep, Keccak-f[1600] with one Keccak lane per SIMD lane.
+#include "blitzar_amd/csrc/proof/sumcheck_transcript.h"
+
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "blitzar_amd/csrc/proof/sumcheck_rows.h"
+#include "blitzar_amd/csrc/proof/transcript.h"
+
+namespace bz::proof {
+namespace {
+// pairs of rows from which on one workgroup finishes the proof
+constexpr u32 kTailRows = 256;
+
+u32 variables_of(u64 n) {
+  u32 v = 0;
+  while ((u64{1} << v) < n) ++v;
+  return v == 0 ? 1 : v;
+}
+
+//--------------------------------------------------------------------------------------------------
+// the protocol, over the sponge of the host or of a wavefront
+//--------------------------------------------------------------------------------------------------
+// r from the 32 challenge bytes x: writes r in the caller's representation, returns it in engine form
+template <class E> struct challenge;
+template <> struct challenge<scalar25519_elements> {
+  using F = scalar25_field;
+  BZ_HD static F::fe make(u8* r_bytes, const u8* x) {
+    const F::fe r = scalar25519_elements::load(x); // any 256-bit integer: V < 16 before the product
+    scalar25519_elements::store(r_bytes, r);
+    return r;
+  }
+};
+template <> struct challenge<grumpkin_elements> {
+  using F = grumpkin_fq29;
+  BZ_HD static F::fe make(u8* r_bytes, const u8* x) {
+    // load() takes x for Montgomery limbs (x < 2^256: V < 6 before the product): the value x / 2^256;
+    // one more product takes the engine's R out and leaves that value as a plain integer
+    F::fe plain_one = F::zero();
+    plain_one.v[0] = 1;
+    const F::fe y = F::mul(grumpkin_elements::load(x), plain_one);
+    u64 w[4];
+    F::to_words(w, F::canonical(y));
+    std::memcpy(r_bytes, w, 32);
+    return F::from_mont64(w);
+  }
+};
+
+template <class Sponge> BZ_HD void transcript_begin(transcript_state* t, u64 num_variables, u64 degree) {
+  transcript_over<Sponge> tr{t};
+  tr.set_domain(label("sumcheck proof v1"));
+  tr.append_u64(label("n"), num_variables);
+  tr.append_u64(label("k"), degree);
+}
+// `x`: 32 bytes for the squeezed challenge (LDS for a wavefront)
+template <class E, class Sponge>
+BZ_HD typename E::F::fe transcript_round(u8* r_bytes, u8* x, transcript_state* t, const u8* polynomial,
+                                         u32 length) {
+  transcript_over<Sponge> tr{t};
+  tr.append_message(label("P"), polynomial, static_cast<size_t>(32) * length);
+  tr.challenge_bytes(x, 32, label("R"));
+  return challenge<E>::make(r_bytes, x);
+}
+
+//--------------------------------------------------------------------------------------------------
+// device kernels
+//--------------------------------------------------------------------------------------------------
+// what wavefront 0 keeps in LDS for the transcript
+struct alignas(8) wave_transcript {
+  transcript_state t;
+  u8 pad[5];
+  u8 message[(kMaxDegree + 1) * 32]; // the round polynomial in the caller's representation
+  u8 x[32], r[32];
+};
+
+BZ_DEV void load_transcript(wave_transcript& w, const u8* transcript) {
+  u8* t = reinterpret_cast<u8*>(&w.t);
+  for (u32 i = threadIdx.x; i < sizeof(transcript_state); i += 64) t[i] = transcript[i];
+  wave_sponge::sync();
+}
+BZ_DEV void store_transcript(u8* transcript, const wave_transcript& w) {
+  const u8* t = reinterpret_cast<const u8*>(&w.t);
+  for (u32 i = threadIdx.x; i < sizeof(transcript_state); i += 64) transcript[i] = t[i];
+}
+
+// A round's transcript step, by the 64 lanes of wavefront 0: sum[0 .. length) (LDS) is the round
+// polynomial; stores it and the challenge in the caller's representation, leaves r and 1 - r in
+// engine form in slot[0], slot[1]
+template <class E>
+BZ_DEV void wave_round(wave_transcript& w, const typename E::F::fe* sum, u32 length, u8* polynomial,
+                       u8* point, typename E::F::fe* slot) {
+  using F = typename E::F;
+  const u32 lane = threadIdx.x;
+  if (lane < length) E::store(w.message + 32 * lane, sum[lane]);
+  wave_sponge::sync();
+  for (u32 i = lane; i < 32 * length; i += 64) polynomial[i] = w.message[i];
+  const typename F::fe r = transcript_round<E, wave_sponge>(w.r, w.x, &w.t, w.message, length);
+  wave_sponge::sync();
+  if (lane < 32) point[lane] = w.r[lane];
+  if (lane == 0) {
+    slot[0] = r;
+    slot[1] = fsub<F>(F::one(), r);
+  }
+}
+
+// One workgroup, in the place of k_sumcheck_finish: adds the workgroups' partials, then the
+// round's transcript step (round 0: the transcript's init first)
+template <class E>
+__global__ void __launch_bounds__(kRoundThreads)
+    k_sumcheck_challenge(u8* __restrict__ polynomials, u8* __restrict__ evaluation_point,
+                         typename E::F::fe* __restrict__ slot, u8* __restrict__ transcript,
+                         const typename E::F::fe* __restrict__ partials, u32 blocks, u32 length,
+                         u32 round, u32 num_variables) {
+  using F = typename E::F;
+  using fe = typename F::fe;
+  __shared__ fe tree[kRoundThreads];
+  __shared__ fe sum[kMaxDegree + 1];
+  __shared__ wave_transcript w;
+  for (u32 k = 0; k < length; ++k) {
+    fe mine = F::zero();
+    for (u32 b = threadIdx.x; b < blocks; b += kRoundThreads) {
+      mine = fadd<F>(mine, partials[static_cast<u64>(b) * (kMaxDegree + 1) + k]);
+    }
+    const fe total = block_sum<F>(tree, mine);
+    if (threadIdx.x == 0) sum[k] = total;
+  }
+  __syncthreads();
+  if (threadIdx.x >= 64) return;
+  load_transcript(w, transcript);
+  if (round == 0) transcript_begin<wave_sponge>(&w.t, num_variables, length - 1);
+  wave_round<E>(w, sum, length, polynomials + static_cast<size_t>(32) * length * round,
+                evaluation_point + static_cast<size_t>(32) * round, slot);
+  store_transcript(transcript, w);
+}
+
+// k_sumcheck_fold with r and 1 - r from the slot; the last fold (`evaluations`, mid = 1) goes to
+// the caller in the caller's representation
+template <class E>
+__global__ void __launch_bounds__(256)
+    k_sumcheck_fold_slot(typename E::F::fe* __restrict__ out, u8* __restrict__ evaluations,
+                         const typename E::F::fe* __restrict__ in, u64 n, u64 mid, u32 num_mles,
+                         const typename E::F::fe* __restrict__ slot) {
+  using F = typename E::F;
+  const u64 id = static_cast<u64>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (id >= mid * num_mles) return;
+  const u64 m = id / mid, i = id % mid;
+  typename F::fe v = F::mul(in[m * n + i], slot[1]);
+  if (mid + i < n) v = fadd<F>(v, F::mul(slot[0], in[m * n + mid + i]));
+  if (evaluations != nullptr) {
+    E::store(evaluations + E::element_bytes * id, v);
+  } else {
+    out[id] = v;
+  }
+}
+
+// Rounds first_round .. v - 1 in one workgroup (2^(v - 1 - first_round) <= kTailRows pairs of
+// rows): per round the workgroup sums the round polynomial, wavefront 0 runs the transcript step,
+// r and 1 - r come back through LDS, the fold writes the other table (not in place: the layout
+// changes from m n + i to m mid + i).  The last fold goes to `evaluations` (may be null).
+template <class E, u32 D>
+__global__ void __launch_bounds__(kRoundThreads)
+    k_sumcheck_tail(u8* __restrict__ polynomials, u8* __restrict__ evaluation_point,
+                    u8* __restrict__ evaluations, u8* __restrict__ transcript,
+                    typename E::F::fe* table_in, typename E::F::fe* table_out, u64 n, u32 num_mles,
+                    const product_desc<typename E::F>* __restrict__ products, u32 num_products,
+                    const u32* __restrict__ terms, u32 first_round, u32 num_variables) {
+  using F = typename E::F;
+  using fe = typename F::fe;
+  __shared__ fe tree[D + 1][kRoundThreads];
+  __shared__ fe sum[D + 1];
+  __shared__ fe slot[2];
+  __shared__ wave_transcript w;
+  const bool wave0 = threadIdx.x < 64;
+  if (wave0) {
+    load_transcript(w, transcript);
+    if (first_round == 0) transcript_begin<wave_sponge>(&w.t, num_variables, D);
+  }
+  for (u32 round = first_round; round < num_variables; ++round) {
+    const u32 mid = 1u << (num_variables - 1 - round);
+    fe poly[D + 1];
+#pragma unroll
+    for (u32 k = 0; k <= D; ++k) poly[k] = F::zero();
+    const dense_tables<F> tables{table_in, n, mid};
+    for (u32 i = threadIdx.x; i < mid; i += kRoundThreads) {
+      accumulate_row_fixed<F, D>(poly, tables, i, products, num_products, terms);
+    }
+    store_partials<F, D>(sum, tree, poly);
+    __syncthreads();
+    if (wave0) {
+      wave_round<E>(w, sum, D + 1, polynomials + static_cast<size_t>(32) * (D + 1) * round,
+                    evaluation_point + static_cast<size_t>(32) * round, slot);
+    }
+    __syncthreads();
+    const bool last = round + 1 == num_variables;
+    if (last && evaluations == nullptr) break;
+    const fe r = slot[0], one_minus_r = slot[1];
+    for (u32 id = threadIdx.x; id < mid * num_mles; id += kRoundThreads) {
+      const u32 m = id / mid, i = id % mid;
+      fe v = F::mul(table_in[m * n + i], one_minus_r);
+      if (mid + i < n) v = fadd<F>(v, F::mul(r, table_in[m * n + mid + i]));
+      if (last) {
+        E::store(evaluations + E::element_bytes * id, v);
+      } else {
+        table_out[id] = v;
+      }
+    }
+    __syncthreads();
+    fe* const folded = table_out;
+    table_out = table_in;
+    table_in = folded;
+    n = mid;
+  }
+  if (wave0) store_transcript(transcript, w);
+}
+
+template <class E, u32 D>
+void launch_tail(hipStream_t stream, u32 degree, u8* polynomials, u8* evaluation_point,
+                 u8* evaluations, u8* transcript, typename E::F::fe* table_in,
+                 typename E::F::fe* table_out, u64 n, u32 num_mles,
+                 const product_desc<typename E::F>* products, u32 num_products, const u32* terms,
+                 u32 first_round, u32 num_variables) {
+  if (degree == D) {
+    hipLaunchKernelGGL((k_sumcheck_tail<E, D>), dim3(1), dim3(kRoundThreads), 0, stream, polynomials,
+                       evaluation_point, evaluations, transcript, table_in, table_out, n, num_mles,
+                       products, num_products, terms, first_round, num_variables);
+    return;
+  }
+  if constexpr (D < kFixedDegree) {
+    launch_tail<E, D + 1>(stream, degree, polynomials, evaluation_point, evaluations, transcript,
+                          table_in, table_out, n, num_mles, products, num_products, terms,
+                          first_round, num_variables);
+  }
+}
+
+//--------------------------------------------------------------------------------------------------
+// the caller's workspace
+//--------------------------------------------------------------------------------------------------
+template <class F> struct workspace_layout {
+  using fe = typename F::fe;
+  size_t table, folded, partials, slot, products, terms, total;
+  explicit workspace_layout(const sumcheck_inputs& d) {
+    const u32 v = variables_of(d.n);
+    size_t at = 256; // whatever the caller's pointer lacks to a multiple of 256
+    auto take = [&at](size_t bytes) {
+      const size_t here = at;
+      at += device_arena::padded(bytes);
+      return here;
+    };
+    table = take(sizeof(fe) * d.n * d.num_mles);
+    folded = take(sizeof(fe) * (u64{1} << (v - 1)) * d.num_mles);
+    partials = take(sizeof(fe) * kRoundBlocks * (kMaxDegree + 1));
+    slot = take(sizeof(fe) * 2);
+    products = take(sizeof(product_desc<F>) * d.num_products);
+    terms = take(sizeof(u32) * d.num_product_terms);
+    total = at;
+  }
+};
+
+// Pinned staging for the products and terms: the copies are enqueued from memory that outlives
+// the call.  A slot is reused after kSlots calls; waiting for its last copy is the only wait of
+// the device form on the host.  Never destroyed (the runtime may be gone by then).
+std::mutex g_stage_mutex;
+host_stage_ring& stage_ring() {
+  static host_stage_ring* ring = new host_stage_ring;
+  return *ring;
+}
+
+template <class E>
+void prove_device(u8* polynomials, u8* evaluation_point, u8* mle_evaluations, u8* transcript,
+                  const sumcheck_inputs& d, void* workspace, u64 workspace_bytes, hipStream_t stream) {
+  using F = typename E::F;
+  using fe = typename F::fe;
+  const u32 degree = d.round_degree;
+  const u32 length = degree + 1;
+  const u32 num_variables = variables_of(d.n);
+  const std::vector<product_desc<F>> products = engine_products<E>(d);
+  const workspace_layout<F> layout{d};
+  BZ_RELEASE_ASSERT(workspace != nullptr && workspace_bytes >= layout.total,
+                    "the sumcheck workspace is too small");
+  const uintptr_t address = reinterpret_cast<uintptr_t>(workspace);
+  u8* base = static_cast<u8*>(workspace) + ((256 - address % 256) % 256) - 256;
+  fe* d_mles = reinterpret_cast<fe*>(base + layout.table);
+  fe* d_next = reinterpret_cast<fe*>(base + layout.folded);
+  fe* d_partials = reinterpret_cast<fe*>(base + layout.partials);
+  fe* d_slot = reinterpret_cast<fe*>(base + layout.slot);
+  auto* d_products = reinterpret_cast<product_desc<F>*>(base + layout.products);
+  u32* d_terms = reinterpret_cast<u32*>(base + layout.terms);
+
+  {
+    const size_t product_bytes = sizeof(product_desc<F>) * products.size();
+    const size_t term_bytes = sizeof(u32) * d.num_product_terms;
+    const std::lock_guard<std::mutex> lock{g_stage_mutex};
+    u8* staged = static_cast<u8*>(stage_ring().acquire(product_bytes + term_bytes));
+    std::memcpy(staged, products.data(), product_bytes);
+    std::memcpy(staged + product_bytes, d.product_terms, term_bytes);
+    BZ_HIP_CHECK(hipMemcpyAsync(d_products, staged, product_bytes, hipMemcpyHostToDevice, stream));
+    BZ_HIP_CHECK(hipMemcpyAsync(d_terms, staged + product_bytes, term_bytes, hipMemcpyHostToDevice,
+                                stream));
+    stage_ring().release(stream);
+  }
+
+  u64 n = d.n;
+  launch_sumcheck_load<E>(stream, d_mles, static_cast<const u8*>(d.mles), n * d.num_mles);
+  BZ_HIP_CHECK(hipGetLastError());
+  g_kernel_launches += 1;
+  for (u32 round = 0; round < num_variables; ++round) {
+    const u64 mid = u64{1} << (num_variables - 1 - round);
+    if (degree <= kFixedDegree && mid <= kTailRows) {
+      launch_tail<E, 1>(stream, degree, polynomials, evaluation_point, mle_evaluations, transcript,
+                        d_mles, d_next, n, d.num_mles, d_products, d.num_products, d_terms, round,
+                        num_variables);
+      BZ_HIP_CHECK(hipGetLastError());
+      g_kernel_launches += 1;
+      return;
+    }
+    const u32 blocks =
+        static_cast<u32>(std::min<u64>(kRoundBlocks, (mid + kRoundThreads - 1) / kRoundThreads));
+    launch_sumcheck_round<F>(stream, blocks, d_partials, d_mles, n, mid, d_products, d.num_products,
+                             d_terms, degree);
+    BZ_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL((k_sumcheck_challenge<E>), dim3(1), dim3(kRoundThreads), 0, stream,
+                       polynomials, evaluation_point, d_slot, transcript, d_partials, blocks, length,
+                       round, num_variables);
+    BZ_HIP_CHECK(hipGetLastError());
+    g_kernel_launches += 2;
+    const bool last = round + 1 == num_variables;
+    if (last && mle_evaluations == nullptr) return;
+    hipLaunchKernelGGL((k_sumcheck_fold_slot<E>), dim3(ceil_div_u32(mid * d.num_mles, 256)),
+                       dim3(256), 0, stream, d_next, last ? mle_evaluations : nullptr, d_mles, n,
+                       mid, d.num_mles, d_slot);
+    BZ_HIP_CHECK(hipGetLastError());
+    g_kernel_launches += 1;
+    std::swap(d_mles, d_next);
+    n = mid;
+  }
+}
+
+// the GPU backend's form on host operands: upload, the device chain on the primary stream,
+// download, one synchronise
+template <class E>
+void prove_uploaded(api_state& st, u8* polynomials, u8* evaluation_point, u8* mle_evaluations,
+                    u8* transcript, const sumcheck_inputs& d) {
+  using F = typename E::F;
+  const int device = st.primary().device;
+  hipStream_t stream = st.primary().stream;
+  BZ_HIP_CHECK(hipSetDevice(device));
+  const u32 num_variables = variables_of(d.n);
+  const size_t raw_bytes = static_cast<size_t>(E::element_bytes) * d.n * d.num_mles;
+  const size_t poly_bytes = static_cast<size_t>(32) * (d.round_degree + 1) * num_variables;
+  const size_t point_bytes = static_cast<size_t>(32) * num_variables;
+  const size_t evaluation_bytes = static_cast<size_t>(32) * d.num_mles;
+  const workspace_layout<F> layout{d};
+  const size_t arena_bytes = device_arena::padded(raw_bytes) + device_arena::padded(poly_bytes) +
+                             device_arena::padded(point_bytes) +
+                             device_arena::padded(evaluation_bytes) + 256 + layout.total;
+  g_sumcheck_arena_bytes.store(arena_bytes);
+  device_arena own;
+  own.reset(arena_bytes, stream);
+  u8* d_raw = own.take<u8>(raw_bytes);
+  u8* d_polynomials = own.take<u8>(poly_bytes);
+  u8* d_point = own.take<u8>(point_bytes);
+  u8* d_evaluations = own.take<u8>(evaluation_bytes);
+  u8* d_transcript = own.take<u8>(sizeof(transcript_state));
+  u8* d_workspace = own.take<u8>(layout.total);
+  BZ_HIP_CHECK(hipMemcpyAsync(d_raw, d.mles, raw_bytes, hipMemcpyHostToDevice, stream));
+  BZ_HIP_CHECK(hipMemcpyAsync(d_transcript, transcript, sizeof(transcript_state),
+                              hipMemcpyHostToDevice, stream));
+  sumcheck_inputs on_device = d;
+  on_device.mles = d_raw;
+  prove_device<E>(d_polynomials, d_point, mle_evaluations != nullptr ? d_evaluations : nullptr,
+                  d_transcript, on_device, d_workspace, layout.total, stream);
+  BZ_HIP_CHECK(hipMemcpyAsync(polynomials, d_polynomials, poly_bytes, hipMemcpyDeviceToHost, stream));
+  BZ_HIP_CHECK(hipMemcpyAsync(evaluation_point, d_point, point_bytes, hipMemcpyDeviceToHost, stream));
+  if (mle_evaluations != nullptr) {
+    BZ_HIP_CHECK(hipMemcpyAsync(mle_evaluations, d_evaluations, evaluation_bytes,
+                                hipMemcpyDeviceToHost, stream));
+  }
+  BZ_HIP_CHECK(hipMemcpyAsync(transcript, d_transcript, sizeof(transcript_state),
+                              hipMemcpyDeviceToHost, stream));
+  BZ_HIP_CHECK(hipStreamSynchronize(stream));
+  own.release();
+}
+
+struct round_context {
+  void* transcript;
+  unsigned field_id;
+};
+void round_callback(void* r, void* context, const void* polynomial, unsigned length) {
+  const auto* c = static_cast<const round_context*>(context);
+  sumcheck_transcript_round(r, c->transcript, c->field_id, polynomial, length);
+}
+
+template <class E>
+bool verify(u8* expected_sum, u8* evaluation_point, transcript_state* t, const u8* polynomials,
+            u32 num_variables, u32 degree) {
+  using F = typename E::F;
+  using fe = typename F::fe;
+  transcript_begin<host_sponge>(t, num_variables, degree);
+  fe expected = E::load(expected_sum);
+  for (u32 round = 0; round < num_variables; ++round) {
+    const u8* p = polynomials + static_cast<size_t>(32) * (degree + 1) * round;
+    // p(0) + p(1) (polynomial_utility.h sum_polynomial_01)
+    fe sum = fadd<F>(E::load(p), E::load(p));
+    for (u32 k = 1; k <= degree; ++k) sum = fadd<F>(sum, E::load(p + 32 * k));
+    u8 have[32], want[32];
+    E::store(have, sum);
+    E::store(want, expected);
+    if (std::memcmp(have, want, 32) != 0) return false;
+    u8 x[32];
+    const fe r = transcript_round<E, host_sponge>(evaluation_point + static_cast<size_t>(32) * round,
+                                                  x, t, p, degree + 1);
+    // p(r) by Horner (polynomial_utility.h evaluate_polynomial)
+    expected = E::load(p + 32 * degree);
+    for (u32 k = degree; k-- > 0;) expected = fadd<F>(F::mul(expected, r), E::load(p + 32 * k));
+    E::store(expected_sum, expected);
+  }
+  return true;
+}
+} // namespace
+
+void sumcheck_transcript_begin(void* transcript, u64 num_variables, u64 round_degree) {
+  transcript_begin<host_sponge>(static_cast<transcript_state*>(transcript), num_variables,
+                                round_degree);
+}
+
+void sumcheck_transcript_round(void* r, void* transcript, unsigned field_id, const void* polynomial,
+                               unsigned length) {
+  auto* t = static_cast<transcript_state*>(transcript);
+  u8 x[32];
+  if (field_id == 0) {
+    transcript_round<scalar25519_elements, host_sponge>(static_cast<u8*>(r), x, t,
+                                                        static_cast<const u8*>(polynomial), length);
+  } else if (field_id == 1) {
+    transcript_round<grumpkin_elements, host_sponge>(static_cast<u8*>(r), x, t,
+                                                     static_cast<const u8*>(polynomial), length);
+  } else {
+    BZ_RELEASE_ASSERT(false, "unsupported field id");
+  }
+}
+
+void prove_sumcheck_transcript(api_state& st, void* polynomials, void* evaluation_point,
+                               void* mle_evaluations, void* transcript, unsigned field_id,
+                               const sumcheck_inputs& d) {
+  check_sumcheck_limits(d);
+  BZ_RELEASE_ASSERT(field_id <= 1, "unsupported field id");
+  if (st.backend != 2) {
+    // the host round loop with the host Merlin as its callback
+    sumcheck_transcript_begin(transcript, variables_of(d.n), d.round_degree);
+    round_context context{transcript, field_id};
+    prove_sumcheck(st, polynomials, evaluation_point, mle_evaluations, field_id, d,
+                   reinterpret_cast<void*>(&round_callback), &context);
+    return;
+  }
+  if (field_id == 0) {
+    prove_uploaded<scalar25519_elements>(st, static_cast<u8*>(polynomials),
+                                         static_cast<u8*>(evaluation_point),
+                                         static_cast<u8*>(mle_evaluations),
+                                         static_cast<u8*>(transcript), d);
+  } else {
+    prove_uploaded<grumpkin_elements>(st, static_cast<u8*>(polynomials),
+                                      static_cast<u8*>(evaluation_point),
+                                      static_cast<u8*>(mle_evaluations),
+                                      static_cast<u8*>(transcript), d);
+  }
+}
+
+u64 sumcheck_transcript_workspace_bytes(unsigned field_id, const sumcheck_inputs& d) {
+  check_sumcheck_limits(d);
+  BZ_RELEASE_ASSERT(field_id <= 1, "unsupported field id");
+  return field_id == 0 ? workspace_layout<scalar25_field>{d}.total
+                       : workspace_layout<grumpkin_fq29>{d}.total;
+}
+
+void prove_sumcheck_transcript_device(void* polynomials, void* evaluation_point,
+                                      void* mle_evaluations, void* transcript, unsigned field_id,
+                                      const sumcheck_inputs& d, void* workspace, u64 workspace_bytes,
+                                      hipStream_t stream) {
+  check_sumcheck_limits(d);
+  if (field_id == 0) {
+    prove_device<scalar25519_elements>(static_cast<u8*>(polynomials),
+                                       static_cast<u8*>(evaluation_point),
+                                       static_cast<u8*>(mle_evaluations),
+                                       static_cast<u8*>(transcript), d, workspace, workspace_bytes,
+                                       stream);
+  } else if (field_id == 1) {
+    prove_device<grumpkin_elements>(static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
+                                    static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript),
+                                    d, workspace, workspace_bytes, stream);
+  } else {
+    BZ_RELEASE_ASSERT(false, "unsupported field id");
+  }
+}
+
+bool verify_sumcheck(void* expected_sum, void* evaluation_point, void* transcript, unsigned field_id,
+                     const void* round_polynomials, unsigned num_variables, unsigned round_degree) {
+  BZ_RELEASE_ASSERT(num_variables > 0 && round_degree > 0,
+                    "sumcheck verification needs num_variables > 0 and round_degree > 0");
+  auto* t = static_cast<transcript_state*>(transcript);
+  if (field_id == 0) {
+    return verify<scalar25519_elements>(static_cast<u8*>(expected_sum),
+                                        static_cast<u8*>(evaluation_point), t,
+                                        static_cast<const u8*>(round_polynomials), num_variables,
+                                        round_degree);
+  }
+  BZ_RELEASE_ASSERT(field_id == 1, "unsupported field id");
+  return verify<grumpkin_elements>(static_cast<u8*>(expected_sum), static_cast<u8*>(evaluation_point),
+                                   t, static_cast<const u8*>(round_polynomials), num_variables,
+                                   round_degree);
+}
+} // namespace bz::proof

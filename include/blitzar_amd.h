@@ -330,6 +330,61 @@ void bzamd_prove_sumcheck_device_columns(void* polynomials, void* evaluation_poi
  * working tables, staged operands and round buffers (0 before the first one). */
 uint64_t bzamd_sumcheck_device_bytes(void);
 
+
+/* Sumcheck with the library's own transcript: the reference's prfsk::reference_transcript over the
+ * caller's 203-byte Merlin state, used in place; its state after a call is part of the contract.
+ *   init, for v = max(ceil_log2(n), 1) variables and round degree D:
+ *     append_message("domain-sep", "sumcheck proof v1"), append_message("n", u64 LE v),
+ *     append_message("k", u64 LE D)
+ *   every round: append_message("P", the (D + 1) 32 bytes of the round polynomial as written to
+ *     `polynomials`), x = challenge_bytes("R", 32), and the challenge from x by field:
+ *     SXT_FIELD_SCALAR255: the little-endian integer x mod l; SXT_FIELD_GRUMPKIN: the bytes the
+ *     reference makes of x (the canonical integer x / 2^256 mod p), taken as the element.
+ *
+ * The transcript as a callback for sxt_prove_sumcheck / bzamd_prove_sumcheck*: call
+ * bzamd_sumcheck_transcript_begin once, then pass bzamd_sumcheck_transcript_round as
+ * transcript_callback and a bzamd_sumcheck_transcript_context as transcript_context. */
+struct bzamd_sumcheck_transcript_context {
+  struct sxt_transcript* transcript;
+  unsigned field_id;
+};
+void bzamd_sumcheck_transcript_begin(struct sxt_transcript* transcript, uint64_t num_variables,
+                                     uint64_t round_degree);
+void bzamd_sumcheck_transcript_round(void* r, void* context, const void* polynomial, unsigned length);
+
+/* bzamd_prove_sumcheck with that transcript built in (init included).  HOST operands, blocking,
+ * cpu and gpu backends; outputs as bzamd_prove_sumcheck.  The gpu backend runs the device form
+ * below on uploaded operands and synchronises once, at the end. */
+void bzamd_prove_sumcheck_transcript(void* polynomials, void* evaluation_point, void* mle_evaluations,
+                                     struct sxt_transcript* transcript, unsigned field_id,
+                                     const struct sumcheck_descriptor* descriptor);
+
+/* The prover that never returns to the host between rounds.  DEVICE pointers on the current HIP
+ * device: descriptor->mles (read only), polynomials, evaluation_point, mle_evaluations (may be
+ * NULL), transcript (203 bytes, in / out) and workspace (bzamd_sumcheck_transcript_workspace_bytes
+ * of the same field and descriptor, at least; less aborts).  HOST: the descriptor, the product
+ * table and the terms, which are read before the call returns.  gpu backend only.  The call only
+ * enqueues on `stream`: no synchronise, no allocation, no callback; outputs, transcript and
+ * workspace are the caller's to reuse once the work enqueued by the call has completed.  Limits
+ * and aborts are those of bzamd_prove_sumcheck_device. */
+uint64_t bzamd_sumcheck_transcript_workspace_bytes(unsigned field_id,
+                                                   const struct sumcheck_descriptor* descriptor);
+void bzamd_prove_sumcheck_transcript_device(void* polynomials, void* evaluation_point,
+                                            void* mle_evaluations, void* transcript,
+                                            unsigned field_id,
+                                            const struct sumcheck_descriptor* descriptor,
+                                            void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* The matching verifier (the reference's prfsk::verify_sumcheck_no_evaluation with that
+ * transcript): host arithmetic only, needs no backend.  round_polynomials: num_variables x
+ * (round_degree + 1) elements.  Every round checks 2 p[0] + p[1] + .. + p[D] == expected_sum, draws
+ * r into evaluation_point and sets expected_sum = p(r).  expected_sum: in = the claimed sum, out =
+ * the value the caller's final evaluation must equal.  Returns 1, or 0 at the first round whose
+ * check fails: outputs and transcript are then as the rounds before it left them. */
+int bzamd_verify_sumcheck(void* expected_sum, void* evaluation_point, struct sxt_transcript* transcript,
+                          unsigned field_id, const void* round_polynomials, unsigned num_variables,
+                          unsigned round_degree);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

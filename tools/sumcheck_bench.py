@@ -4,7 +4,7 @@ benchmark/sumcheck/benchmark.m.cc (degree x num_products random MLEs of n rows, 
 length `degree`, a hash transcript), for both fields of the ABI.
 
     python tools/sumcheck_bench.py <n> <degree> <num_products> <num_samples> [--fields 0,1]
-                                   [--column-bytes 1|2|4|8]
+                                   [--column-bytes 1|2|4|8] [--transcript]
 
 Timed, with a device synchronise inside the clock, after one untimed call:
   host    sxt_prove_sumcheck: the tables start in host memory (their upload is part of the call);
@@ -16,6 +16,13 @@ those values widened to 32 bytes, and two more legs run beside them on resident 
 Both must return the device leg's bytes; `device_bytes` is the device memory each form allocated.
 The transcript callback is Python (one ctypes call and one SHA-256 per round); its cost is timed
 alone and printed beside the two (`callback_ms`) -- it is inside both figures and is not kernel time.
+With --transcript the transcript is the library's own Merlin (the reference's reference_transcript)
+and two legs on resident tables alternate in one process, A, B, A, B, ..., after one untimed call each:
+  A  bzamd_prove_sumcheck_device with the native bzamd_sumcheck_transcript_round as its callback (no
+     Python in the loop; one host round trip per round);
+  B  bzamd_prove_sumcheck_transcript_device: enqueue only, timed to a stream synchronise after it.
+Both must leave the same bytes.  Printed per field: the medians, the spread of the A samples (max -
+min) and whether B's median is within that spread of A's or better (`b_not_slower`).
 BLITZAR_AMD_LIB selects the library (A/B against another build in one session); a library without
 bzamd_prove_sumcheck_device reports the device leg as absent.  Prints one JSON line.  Needs a GPU:
 there is no CPU fallback."""
@@ -102,6 +109,68 @@ def summary(ms):
             "max_ms": round(max(ms), 4), "samples_ms": [round(x, 4) for x in ms]}
 
 
+def transcript_legs(field_id, dev, n, degree, num_products, num_samples):
+    """--transcript: legs A and B of the docstring for one field"""
+    num_mles = degree * num_products
+    rounds = max((n - 1).bit_length(), 1)
+    rng = np.random.default_rng(1 + field_id)
+    mles = random_elements(rng, field_id, n * num_mles).reshape(num_mles, n, 32)
+    table = np.zeros((num_products, api.SUMCHECK_PRODUCT_STRIDE[field_id]), np.uint8)
+    table[:, :32] = random_elements(rng, field_id, num_products)
+    table[:, 32:36] = np.frombuffer(np.uint32(degree).tobytes(), np.uint8)
+    terms = np.arange(num_mles, dtype=np.uint32)
+    d_mles = torch.from_numpy(mles).to(dev)
+    t0 = api.transcript_new("sumcheck bench")
+    out = {}
+    t_a = t0.copy()
+    context = api.bzamd_sumcheck_transcript_context(t_a.ctypes.data, field_id)
+
+    def leg_a():
+        t_a[:] = t0
+        api.sumcheck_transcript_begin(t_a, rounds, degree)
+        out["a"] = api.prove_sumcheck_device(field_id, d_mles.data_ptr(), num_mles, table, terms, n,
+                                             degree, api.SUMCHECK_TRANSCRIPT_ROUND,
+                                             context=ctypes.addressof(context))
+
+    d_t0 = torch.from_numpy(t0).to(dev)
+    d_t = torch.zeros_like(d_t0)
+    d_polys = torch.zeros((rounds, degree + 1, 32), dtype=torch.uint8, device=dev)
+    d_point = torch.zeros((rounds, 32), dtype=torch.uint8, device=dev)
+    d_evaluations = torch.zeros((num_mles, 32), dtype=torch.uint8, device=dev)
+    workspace_bytes = api.sumcheck_transcript_workspace_bytes(field_id, n, num_mles, num_products,
+                                                              num_mles, degree)
+    d_workspace = torch.empty(workspace_bytes, dtype=torch.uint8, device=dev)
+
+    def leg_b():
+        d_t.copy_(d_t0)
+        api.prove_sumcheck_transcript_device(
+            field_id, d_mles.data_ptr(), num_mles, table, terms, n, degree, d_polys.data_ptr(),
+            d_point.data_ptr(), d_evaluations.data_ptr(), d_t.data_ptr(), d_workspace.data_ptr(),
+            workspace_bytes, stream=torch.cuda.current_stream(dev).cuda_stream)
+
+    for leg in (leg_a, leg_b):
+        leg()  # warm
+        torch.cuda.synchronize()
+    ms = {"a": [], "b": []}
+    for _ in range(num_samples):
+        for name, leg in (("a", leg_a), ("b", leg_b)):
+            t_start = time.perf_counter()
+            leg()
+            torch.cuda.synchronize()
+            ms[name].append((time.perf_counter() - t_start) * 1e3)
+    got = (d_polys.cpu().numpy(), d_point.cpu().numpy(), d_evaluations.cpu().numpy())
+    same = all(np.array_equal(a, b) for a, b in zip(out["a"], got)) and \
+        np.array_equal(t_a, d_t.cpu().numpy())
+    assert same, "the device transcript form disagrees with the callback form"
+    a, b = summary(ms["a"]), summary(ms["b"])
+    spread = a["max_ms"] - a["min_ms"]
+    return {"A_callback": a, "B_device_transcript": b, "a_spread_ms": round(spread, 4),
+            "b_over_a": round(b["median_ms"] / a["median_ms"], 4),
+            "b_not_slower": bool(b["median_ms"] <= a["median_ms"] + spread),
+            "b_equals_a": True,
+            "polynomials_sha256": hashlib.sha256(got[0].tobytes()).hexdigest()[:16]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("n", type=int)
@@ -110,6 +179,7 @@ def main():
     ap.add_argument("num_samples", type=int)
     ap.add_argument("--fields", default="0,1")
     ap.add_argument("--column-bytes", type=int, choices=[1, 2, 4, 8], default=None)
+    ap.add_argument("--transcript", action="store_true")
     args = ap.parse_args()
     lib = api.load()
     assert lib.bzamd_device_count() > 0, "sumcheck_bench needs a GPU"
@@ -123,6 +193,15 @@ def main():
     rec = {"n": n, "degree": degree, "num_products": num_products, "num_mles": num_mles,
            "rounds": rounds, "num_samples": args.num_samples, "library": api.LIB_PATH,
            "table_bytes": 32 * n * num_mles, "fields": {}}
+    if args.transcript:
+        assert hasattr(lib, "bzamd_prove_sumcheck_transcript_device"), \
+            "--transcript needs a library with the device transcript form"
+        rec["mode"] = "transcript"
+        for field_id in (int(x) for x in args.fields.split(",")):
+            rec["fields"][str(field_id)] = transcript_legs(field_id, dev, n, degree, num_products,
+                                                           args.num_samples)
+        print(json.dumps(rec), flush=True)
+        return
     if args.column_bytes is not None:
         assert has_device_form and hasattr(lib, "bzamd_prove_sumcheck_device_columns"), \
             "--column-bytes needs a library with the columns form"
