@@ -154,6 +154,14 @@ def load():
     lib.sxt_curve25519_prove_inner_product.restype = None
     lib.sxt_curve25519_verify_inner_product.argtypes = [vp, u64, u64, vp, vp, vp, vp, vp, vp]
     lib.sxt_curve25519_verify_inner_product.restype = ctypes.c_int
+    # (an older build selected with BLITZAR_AMD_LIB lacks these two: tools/inner_product_bench.py
+    # measures against one; calling them there raises AttributeError)
+    if hasattr(lib, "bzamd_prove_inner_product_device"):
+        lib.bzamd_inner_product_workspace_bytes.argtypes = [u64]
+        lib.bzamd_inner_product_workspace_bytes.restype = u64
+        lib.bzamd_prove_inner_product_device.argtypes = [vp, vp, vp, vp, u64, u64, vp, vp, vp, vp,
+                                                         u64, vp]
+        lib.bzamd_prove_inner_product_device.restype = None
     lib.bzamd_transcript_init.argtypes = [vp, ctypes.c_char_p, u64]
     lib.bzamd_transcript_init.restype = None
     lib.bzamd_num_devices.restype = ctypes.c_int
@@ -336,6 +344,25 @@ def prove_inner_product(transcript, n, generators_offset, a_vector, b_vector):
     load().sxt_curve25519_prove_inner_product(_ptr(l), _ptr(r), _ptr(ap), _ptr(t), n,
                                               generators_offset, _ptr(a), _ptr(b))
     return l[:rounds], r[:rounds], ap, t
+
+
+def inner_product_workspace_bytes(n):
+    """bytes of device workspace bzamd_prove_inner_product_device needs for n elements (0 for
+    n = 0 or n > 2^30); needs no backend"""
+    return load().bzamd_inner_product_workspace_bytes(n)
+
+
+def prove_inner_product_device(n, generators_offset, a_device_ptr, b_device_ptr, l_device_ptr,
+                               r_device_ptr, ap_device_ptr, transcript_device_ptr,
+                               workspace_device_ptr, workspace_bytes, generators_device_ptr=None,
+                               stream=None):
+    """bzamd_prove_inner_product_device: every operand is a raw device pointer (e.g.
+    tensor.data_ptr()) on the current device; `generators_device_ptr` None: the built-in
+    generators from `generators_offset`.  Only enqueues on `stream`."""
+    load().bzamd_prove_inner_product_device(l_device_ptr, r_device_ptr, ap_device_ptr,
+                                            transcript_device_ptr, n, generators_offset,
+                                            generators_device_ptr, a_device_ptr, b_device_ptr,
+                                            workspace_device_ptr, workspace_bytes, stream)
 
 
 def verify_inner_product(transcript, n, generators_offset, b_vector, product, a_commit, l_vector,

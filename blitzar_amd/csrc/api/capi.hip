@@ -1557,6 +1557,34 @@ void sxt_curve25519_prove_inner_product(struct sxt_ristretto255_compressed* l_ve
                              reinterpret_cast<const u8*>(b_vector));
 }
 
+uint64_t bzamd_inner_product_workspace_bytes(uint64_t n) {
+  return proof::inner_product_workspace_bytes(n);
+}
+
+void bzamd_prove_inner_product_device(void* l_vector, void* r_vector, void* ap_value,
+                                      void* transcript, uint64_t n, uint64_t generators_offset,
+                                      const void* generators, const void* a_vector,
+                                      const void* b_vector, void* workspace,
+                                      uint64_t workspace_bytes, void* stream) {
+  BZ_RELEASE_ASSERT(transcript != nullptr, "transcript must not be null");
+  BZ_RELEASE_ASSERT(ap_value != nullptr, "ap_value must not be null");
+  BZ_RELEASE_ASSERT(b_vector != nullptr, "b_vector must not be null");
+  BZ_RELEASE_ASSERT(a_vector != nullptr, "a_vector must not be null");
+  BZ_RELEASE_ASSERT(n > 0, "a_vector and b_vector lengths must be greater than zero");
+  BZ_RELEASE_ASSERT(n == 1 || (l_vector != nullptr && r_vector != nullptr),
+                    "l_vector and r_vector must not be null when n is bigger than one");
+  BZ_RELEASE_ASSERT(n <= (uint64_t{1} << 30), "inner products are limited to 2^30 elements");
+  // the current device, the caller's stream and workspace; the engine context locks itself, so no
+  // lease is taken (as bzamd_msm_device)
+  api_state& st = state();
+  BZ_RELEASE_ASSERT(st.backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
+  proof::prove_inner_product_device(
+      *st.context_for_current_device(), static_cast<u8*>(l_vector), static_cast<u8*>(r_vector),
+      static_cast<u8*>(ap_value), transcript, n, generators_offset, generators,
+      static_cast<const u8*>(a_vector), static_cast<const u8*>(b_vector), workspace, workspace_bytes,
+      static_cast<hipStream_t>(stream));
+}
+
 int sxt_curve25519_verify_inner_product(struct sxt_transcript* transcript, uint64_t n,
                                         uint64_t generators_offset,
                                         const struct sxt_curve25519_scalar* b_vector,

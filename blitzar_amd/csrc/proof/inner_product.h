@@ -19,6 +19,16 @@ bool verify_inner_product(api_state& st, void* transcript, u64 n, u64 generators
                           const u8* b_vector, const u8* product, const void* a_commit,
                           const u8* l_vector, const u8* r_vector, const u8* ap_value);
 
+// The device form (include/blitzar_amd.h: bzamd_prove_inner_product_device).  DEVICE pointers on
+// the current device; `generators`: np + 1 elements in ABI layout, the last one Q, or nullptr for
+// the built-in ones from `generators_offset`; `ctx`: the engine context of the current device.
+// Only enqueues on `stream`.  The workspace size depends on np alone (0 for n = 0 or n > 2^30).
+u64 inner_product_workspace_bytes(u64 n);
+void prove_inner_product_device(msm_context& ctx, u8* l_vector, u8* r_vector, u8* ap_value,
+                                void* transcript, u64 n, u64 generators_offset,
+                                const void* generators, const u8* a_vector, const u8* b_vector,
+                                void* workspace, u64 workspace_bytes, hipStream_t stream);
+
 // services of api/capi.hip the prover needs
 // generators [offset, offset + n) as raw extended coordinates on the host (cache + derivation)
 void host_builtin_generators_unlocked(api_state& st, ed_point* out, u64 n, u64 offset);

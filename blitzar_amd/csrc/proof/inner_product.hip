@@ -8,15 +8,23 @@
 // until one element is left.  Proof bytes (compressed L, R; the last a) are canonical encodings
 // of group elements / scalars, so any correct evaluation order reproduces the reference's bytes.
 //
-// Work split (GPU backend): the two MSMs of a round run on the MSM engine with the folded
-// generators resident in HBM (the reference's gpu_driver re-uploads nothing either,
-// gpu_driver.cc:60-130); scalar folds, inner products and the generator fold are kernels below;
-// the transcript, the challenge inversions and the two c Q products are host work.  The host
-// backend runs the same round loop on host loops.
+// The host backend runs the round loop on host loops.  On the device a proof is a chain of kernels
+// enqueued on one stream that never returns to the host: everything lives in
+// the caller's workspace as
+//   scalars     S = [c_l | a_0 .. a_{size-1} | c_r]      (a zero-padded to np; size halves per round)
+//   generators  G = [g_lo (mid) | Q | g_hi (mid)]
+// so that ONE call of the MSM engine with two columns and per-column generator offsets yields
+//   L = rows S[0 .. mid]          over G[mid ..]  = c_l Q + <a_lo, g_hi>,
+//   R = rows S[mid + 1 .. size+1] over G[0 ..]    = <a_hi, g_lo> + c_r Q:
+// the two c Q products are one more row of each column, not a serial double-and-add.  a stays at
+// S + 1 through every fold (in place: entry i is read by its own lane only), c_r moves down to the
+// end of the halved a; the generator fold writes through the terms buffer and re-places Q between
+// the halves of the folded generators.  The transcript step of a round (Merlin on wavefront 0,
+// x mod l, 1 / x, the joint fold digits) is one workgroup that leaves its results in a workspace
+// slot for the fold kernels.
 #include "blitzar_amd/csrc/proof/inner_product.h"
 
 #include <algorithm>
-#include <memory>
 #include <vector>
 
 #include "blitzar_amd/csrc/curve/ed29.h"
@@ -33,6 +41,12 @@ constexpr u32 kScalarBits = 253; // s25cn::max_bits_v
 struct fold_digits {
   u8 d[256];
   u32 count;
+};
+
+// what the challenge kernel leaves in the workspace for the folds of its round
+struct fold_slot {
+  s25::fe x, x_inv;   // Montgomery form
+  fold_digits digits; // of (m_low, m_high) = (x^-1, x)
 };
 
 fold_digits decompose_fold(const u8 m_low[32], const u8 m_high[32]) {
@@ -74,27 +88,113 @@ ed_point scalar_multiply(const ed_point& p, const u8 k[32]) {
 }
 
 //--------------------------------------------------------------------------------------------------
+// the transcript of the protocol, over the sponge of the host or of a wavefront
+// (proof_computation.cc:36-52); prover and verifier, host and device run this text
+//--------------------------------------------------------------------------------------------------
+template <class Sponge> BZ_HD void init_transcript(transcript_state* t, u64 n) {
+  transcript_over<Sponge> tr{t};
+  tr.set_domain(label("inner product proof v1"));
+  tr.append_u64(label("n"), n);
+}
+// `x`: 32 bytes for the squeezed challenge (LDS for a wavefront); returns x mod l in Montgomery
+// form (== s25o::reduce32: every later use is modulo l)
+template <class Sponge>
+BZ_HD s25::fe round_challenge(u8* x, transcript_state* t, const u8* l_value, const u8* r_value) {
+  transcript_over<Sponge> tr{t};
+  tr.append_message(label("L"), l_value, 32);
+  tr.append_message(label("R"), r_value, 32);
+  tr.challenge_bytes(x, 32, label("x"));
+  return s25::to_mont(s25::load(x));
+}
+scalar host_round_challenge(void* transcript_bytes, const u8* l_value, const u8* r_value) {
+  u8 x[32];
+  return {round_challenge<host_sponge>(x, static_cast<transcript_state*>(transcript_bytes), l_value,
+                                       r_value)};
+}
+
+//--------------------------------------------------------------------------------------------------
 // device kernels
 //--------------------------------------------------------------------------------------------------
-// out[i] = m_low x[i] + m_high x[mid + i] (canonical), i < mid; x has `len` entries, the missing
-// high ones count as zero (fold.cc:30-45).  m_* in Montgomery form, x plain: the products are plain.
-// In place (out == x) is safe: entry i is only read by its own lane, entries >= mid are not written.
+constexpr u32 kPartialBlocks = 256; // workgroups of k_inner_product, at most
+
+// Before the first round: a and b into the workspace zero-padded to np (a behind the c_l row), the
+// caller's np + 1 generators into [g_lo | Q | g_hi] (nullptr: the built-in ones were derived in
+// place before this kernel), Q aside for the generator folds.
 __global__ void __launch_bounds__(256)
-    k_fold_scalars(u64* out, const u64* x, s25::fe m_low, s25::fe m_high, u32 mid,
-                   u32 len) {
+    k_load(u64* __restrict__ s, u64* __restrict__ b_out, ed_point* g, ed_point* __restrict__ q,
+           const u8* __restrict__ a, const u8* __restrict__ b, const ed_point* generators, u32 n,
+           u32 np) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  const u32 mid = np / 2;
+  if (i == 0) *q = generators != nullptr ? generators[np] : g[mid];
+  if (i >= np) return;
+  // the caller's scalars are bytes: no alignment is promised
+  const bool aligned = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 7) == 0;
+  for (int k = 0; k < 4; ++k) {
+    u64 wa = 0, wb = 0;
+    if (i < n) {
+      const u64 at = 32 * static_cast<u64>(i) + 8 * k;
+      if (aligned) {
+        wa = *reinterpret_cast<const u64*>(a + at);
+        wb = *reinterpret_cast<const u64*>(b + at);
+      } else {
+        for (int j = 7; j >= 0; --j) {
+          wa = (wa << 8) | a[at + j];
+          wb = (wb << 8) | b[at + j];
+        }
+      }
+    }
+    s[4 * (static_cast<u64>(i) + 1) + k] = wa;
+    b_out[4 * static_cast<u64>(i) + k] = wb;
+  }
+  if (generators != nullptr) {
+    g[i < mid ? i : i + 1] = generators[i];
+    if (i == 0) g[mid] = generators[np];
+  }
+}
+
+// what a wavefront keeps in LDS for a transcript step
+struct alignas(8) wave_state {
+  transcript_state t;
+  u8 pad[5];
+  u8 l[32], r[32], x[32];
+};
+
+// n = 1: the transcript's init, and ap = a[0] verbatim
+__global__ void __launch_bounds__(64)
+    k_single_element(u8* __restrict__ ap, u8* transcript, const u8* __restrict__ a) {
+  __shared__ wave_state w;
+  wave_load_transcript(w.t, transcript);
+  init_transcript<wave_sponge>(&w.t, 1);
+  wave_store_transcript(transcript, w.t);
+  if (threadIdx.x < 32) ap[threadIdx.x] = a[threadIdx.x];
+}
+
+// out[i] = m_low x[i] + m_high x[mid + i] (canonical), i < mid (fold.cc:30-45); (m_low, m_high) =
+// (x, x^-1) for a, (x^-1, x) for b, from the slot in Montgomery form; the vector is plain: the
+// products are plain.  In place (out == in) is safe: entry i is only read by its own lane, entries
+// >= mid are not written.  The last fold of a (mid = 1) goes to the caller as `last`.
+__global__ void __launch_bounds__(256)
+    k_fold_scalars(u64* out, u8* last, const u64* in, const fold_slot* __restrict__ slot,
+                   int low_is_x, u32 mid) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= mid) return;
-  s25::fe r = s25::F::mul(m_low, s25::load_words(x + 4 * static_cast<u64>(i)));
-  if (mid + i < len) {
-    r = s25::add(r, s25::F::mul(m_high, s25::load_words(x + 4 * static_cast<u64>(mid + i))));
+  const s25::fe m_low = low_is_x ? slot->x : slot->x_inv;
+  const s25::fe m_high = low_is_x ? slot->x_inv : slot->x;
+  const s25::fe r =
+      s25::add(s25::F::mul(m_low, s25::load_words(in + 4 * static_cast<u64>(i))),
+               s25::F::mul(m_high, s25::load_words(in + 4 * (static_cast<u64>(mid) + i))));
+  if (last != nullptr) {
+    s25::store(last, r);
+    return;
   }
   u64 w[4];
   s25::store_words(w, r);
   for (int k = 0; k < 4; ++k) out[4 * static_cast<u64>(i) + k] = w[k];
 }
 
-// partials[block] = sum over the block's share of a[i] b[i] / R (plain inputs; the host adds the
-// partials and multiplies by R^2): grid-stride products, LDS tree
+// partials[block] = sum over the block's share of a[i] b[i] / R (plain inputs; k_cross_finish adds
+// the partials and multiplies by R^2): grid-stride products, LDS tree
 __global__ void __launch_bounds__(256)
     k_inner_product(s25::fe* __restrict__ partials, const u64* __restrict__ a,
                     const u64* __restrict__ b, u32 count) {
@@ -114,46 +214,247 @@ __global__ void __launch_bounds__(256)
   if (threadIdx.x == 0) partials[blockIdx.x] = tree[0];
 }
 
-// terms[k * mid + i], k = 0, 1, 2: g_i, g_{mid + i} and their sum as packed cached addends
+// One workgroup: c_l and c_r (canonical) from the `blocks` partials of each, which lie
+// kPartialBlocks apart, into their rows of the scalar columns
+__global__ void __launch_bounds__(kPartialBlocks)
+    k_cross_finish(u64* __restrict__ c_l, u64* __restrict__ c_r,
+                   const s25::fe* __restrict__ partials, u32 blocks) {
+  __shared__ s25::fe tree[kPartialBlocks];
+  for (u32 side = 0; side < 2; ++side) {
+    tree[threadIdx.x] =
+        threadIdx.x < blocks ? partials[side * kPartialBlocks + threadIdx.x] : s25::F::zero();
+    __syncthreads();
+    for (u32 stride = kPartialBlocks / 2; stride > 0; stride >>= 1) {
+      if (threadIdx.x < stride) {
+        tree[threadIdx.x] = s25::add(tree[threadIdx.x], tree[threadIdx.x + stride]);
+      }
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      u64 w[4];
+      s25::store_words(w, s25::F::mul(tree[0], s25::r2()));
+      u64* c = side == 0 ? c_l : c_r;
+      for (int k = 0; k < 4; ++k) c[k] = w[k];
+    }
+    __syncthreads();
+  }
+}
+
+// terms[k * mid + i], k = 0, 1, 2: g_i, g_{mid + 1 + i} (Q lies between the halves) and their sum
+// as packed cached addends
 __global__ void __launch_bounds__(256)
     k_fold_terms(ed29_cached_packed* __restrict__ terms, const ed_point* __restrict__ g, u32 mid) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= mid) return;
-  const ed29_point lo = ed29::from_ed(g[i]), hi = ed29::from_ed(g[mid + i]);
+  const ed29_point lo = ed29::from_ed(g[i]), hi = ed29::from_ed(g[static_cast<u64>(mid) + 1 + i]);
   terms[i] = ed29::pack(ed29::to_cached(lo));
   terms[mid + i] = ed29::pack(ed29::to_cached(hi));
   terms[2 * static_cast<u64>(mid) + i] = ed29::pack(ed29::to_cached(ed29::add(lo, hi)));
 }
 
-// out[i] = m_low g_i + m_high g_{mid + i}: every lane walks the SAME digit sequence (the digits
-// are a kernel argument: uniform control flow), gathering its own three terms
+// g'_i = x^-1 g_i + x g_{mid + i}, written in the next round's layout [g'_lo | Q | g'_hi]: every
+// lane walks the SAME digit sequence (the slot's: wave-uniform loads, uniform control flow),
+// gathering its own three terms.  It reads the terms only, so writing over g is safe.  mid >= 2.
 __global__ void __launch_bounds__(256)
     k_fold_generators(ed_point* __restrict__ out, const ed29_cached_packed* __restrict__ terms,
-                      fold_digits digits, u32 mid) {
+                      const fold_slot* __restrict__ slot, const ed_point* __restrict__ q, u32 mid) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= mid) return;
-  const ed29_point r = fold_point(digits, [&](u32 k) {
+  const ed29_point r = fold_point(slot->digits, [&](u32 k) {
     return ed29::unpack(terms[static_cast<u64>(k) * mid + i]);
   });
-  out[i] = ed29::to_ed(r);
+  const u32 half = mid / 2;
+  out[i < half ? i : i + 1] = ed29::to_ed(r);
+  if (i == 0) out[half] = *q;
+}
+
+// The transcript step of a round, one wavefront: L and R (the engine's encodings, `lr`) go to the
+// caller and into the transcript (round 0, `n` != 0: its init first); x mod l, 1 / x (zero for
+// zero, as scalar::inverse) and the joint digits of (x^-1, x) go to the slot.  Every lane computes
+// the same scalars; the digits are spread over the lanes.
+__global__ void __launch_bounds__(64)
+    k_round_challenge(u8* __restrict__ l_value, u8* __restrict__ r_value,
+                      fold_slot* __restrict__ slot, u8* transcript, const u8* __restrict__ lr, u64 n) {
+  __shared__ wave_state w;
+  const u32 lane = threadIdx.x;
+  wave_load_transcript(w.t, transcript);
+  if (lane < 32) {
+    w.l[lane] = lr[lane];
+    w.r[lane] = lr[32 + lane];
+    l_value[lane] = lr[lane];
+    r_value[lane] = lr[32 + lane];
+  }
+  wave_sponge::sync();
+  if (n != 0) init_transcript<wave_sponge>(&w.t, n);
+  const s25::fe x = round_challenge<wave_sponge>(w.x, &w.t, w.l, w.r);
+  wave_store_transcript(transcript, w.t);
+  const s25::fe x_inv = s25::F::invert(x);
+  u64 lo[4], hi[4];
+  s25::store_words(lo, s25::from_mont(x_inv));
+  s25::store_words(hi, s25::from_mont(x));
+  u32 count = 0;
+#pragma unroll
+  for (u32 k = 0; k < 4; ++k) {
+    const u32 bit = 64 * k + lane;
+    const u32 d = static_cast<u32>((lo[k] >> lane) & 1) + 2 * static_cast<u32>((hi[k] >> lane) & 1);
+    slot->digits.d[bit] = static_cast<u8>(bit < kScalarBits ? d : 0);
+    const u64 any = lo[k] | hi[k];
+    if (any != 0) count = 64 * k + 64 - static_cast<u32>(__builtin_clzll(any));
+  }
+  if (lane == 0) {
+    slot->x = x;
+    slot->x_inv = x_inv;
+    slot->digits.count = count < kScalarBits ? count : kScalarBits;
+  }
 }
 
 //--------------------------------------------------------------------------------------------------
-// the computational backends of the round loop (reference: prfip::driver, driver.h:35-95)
+// the chain
 //--------------------------------------------------------------------------------------------------
-class fold_backend {
-public:
-  virtual ~fold_backend() = default;
-  // c_l = <a_lo, b_hi>, c_r = <a_hi, b_lo> (canonical bytes); l_p = <a_lo, g_hi>, r_p = <a_hi, g_lo>
-  virtual void commit_to_fold(u8 c_l[32], u8 c_r[32], ed_point& l_p, ed_point& r_p) = 0;
-  // a' = x a_lo + x^-1 a_hi; unless one element is left: b' = x^-1 b_lo + x b_hi,
-  // g' = x^-1 g_lo + x g_hi
-  virtual void fold(const scalar& x, const scalar& x_inv) = 0;
-  virtual void first_a(u8 out[32]) = 0;
+u64 ceil_log2(u64 n) {
+  u64 k = 0;
+  while ((u64{1} << k) < n) ++k;
+  return k;
+}
+
+// the caller's workspace, for np = 2^ceil_log2(n)
+struct workspace_layout {
+  size_t scalars, b, generators, terms, partials, slot, q, lr, total;
+  explicit workspace_layout(u64 np) {
+    size_t at = 0;
+    auto take = [&at](size_t bytes) {
+      const size_t here = at;
+      at += device_arena::padded(bytes);
+      return here;
+    };
+    scalars = take(32 * (np + 2));
+    b = take(32 * np);
+    generators = take(sizeof(ed_point) * (np + 1));
+    terms = take(sizeof(ed29_cached_packed) * 3 * (np / 2));
+    partials = take(sizeof(s25::fe) * 2 * kPartialBlocks);
+    slot = take(sizeof(fold_slot));
+    q = take(sizeof(ed_point));
+    lr = take(64);
+    total = at + 256; // whatever the caller's pointer lacks to a multiple of 256
+  }
 };
 
-// current vector shapes, shared by both backends: g has `size` entries, a and b have
-// min(size, their original length) -- only round 0 can be ragged
+void enqueue_chain(msm_context& ctx, u8* l_vector, u8* r_vector, u8* ap_value, u8* transcript, u64 n,
+                   u64 generators_offset, const ed_point* generators, const u8* a_vector,
+                   const u8* b_vector, void* workspace, u64 workspace_bytes, hipStream_t stream) {
+  if (n == 1) {
+    hipLaunchKernelGGL(k_single_element, dim3(1), dim3(64), 0, stream, ap_value, transcript, a_vector);
+    BZ_HIP_CHECK(hipGetLastError());
+    g_kernel_launches += 1;
+    return;
+  }
+  const u64 rounds = ceil_log2(n), np = u64{1} << rounds;
+  const workspace_layout layout{np};
+  BZ_RELEASE_ASSERT(workspace != nullptr && workspace_bytes >= layout.total,
+                    "the inner-product workspace is too small");
+  const uintptr_t address = reinterpret_cast<uintptr_t>(workspace);
+  u8* base = static_cast<u8*>(workspace) + (256 - address % 256) % 256;
+  u64* d_s = reinterpret_cast<u64*>(base + layout.scalars);
+  u64* d_a = d_s + 4; // behind the c_l row
+  u64* d_b = reinterpret_cast<u64*>(base + layout.b);
+  ed_point* d_g = reinterpret_cast<ed_point*>(base + layout.generators);
+  auto* d_terms = reinterpret_cast<ed29_cached_packed*>(base + layout.terms);
+  auto* d_partials = reinterpret_cast<s25::fe*>(base + layout.partials);
+  auto* d_slot = reinterpret_cast<fold_slot*>(base + layout.slot);
+  ed_point* d_q = reinterpret_cast<ed_point*>(base + layout.q);
+  u8* d_lr = base + layout.lr;
+
+  if (generators == nullptr) {
+    builtin_generators_enqueue(d_g, generators_offset, np / 2, stream);
+    builtin_generators_enqueue(d_g + np / 2, generators_offset + np, 1, stream);
+    builtin_generators_enqueue(d_g + np / 2 + 1, generators_offset + np / 2, np / 2, stream);
+    g_kernel_launches += 3;
+  }
+  hipLaunchKernelGGL(k_load, dim3(static_cast<u32>((np + 255) / 256)), dim3(256), 0, stream, d_s,
+                     d_b, d_g, d_q, a_vector, b_vector, generators, static_cast<u32>(n),
+                     static_cast<u32>(np));
+  BZ_HIP_CHECK(hipGetLastError());
+  g_kernel_launches += 1;
+
+  const curve_vtable& vt = curve25519_vtable();
+  u64 round = 0;
+  for (u64 size = np; size > 1; size /= 2, ++round) {
+    const u32 mid = static_cast<u32>(size / 2);
+    const u32 blocks = (mid + 255) / 256;
+    const u32 partial_blocks = std::min(kPartialBlocks, blocks);
+    // c_l = <a_lo, b_hi> into row 0, c_r = <a_hi, b_lo> into the row behind a
+    hipLaunchKernelGGL(k_inner_product, dim3(partial_blocks), dim3(256), 0, stream, d_partials, d_a,
+                       d_b + 4 * static_cast<u64>(mid), mid);
+    hipLaunchKernelGGL(k_inner_product, dim3(partial_blocks), dim3(256), 0, stream,
+                       d_partials + kPartialBlocks, d_a + 4 * static_cast<u64>(mid), d_b, mid);
+    hipLaunchKernelGGL(k_cross_finish, dim3(1), dim3(kPartialBlocks), 0, stream, d_s,
+                       d_a + 4 * size, d_partials, partial_blocks);
+    g_kernel_launches += 3;
+    if (mid > 1) { // does not depend on x: ahead of the engine's kernels
+      hipLaunchKernelGGL(k_fold_terms, dim3(blocks), dim3(256), 0, stream, d_terms, d_g, mid);
+      g_kernel_launches += 1;
+    }
+    BZ_HIP_CHECK(hipGetLastError());
+    // L and R in one call of the engine: generators and scalars are resident
+    host_column col_l = byte_column(reinterpret_cast<const u8*>(d_s), mid + 1, 32, false);
+    col_l.generator_offset = mid;
+    const host_column col_r =
+        byte_column(reinterpret_cast<const u8*>(d_a + 4 * static_cast<u64>(mid)), mid + 1, 32, false);
+    vt.msm(ctx, d_lr, 32, false, {col_l, col_r}, nullptr, d_g, stream);
+    hipLaunchKernelGGL(k_round_challenge, dim3(1), dim3(64), 0, stream, l_vector + 32 * round,
+                       r_vector + 32 * round, d_slot, transcript, d_lr, round == 0 ? n : u64{0});
+    hipLaunchKernelGGL(k_fold_scalars, dim3(blocks), dim3(256), 0, stream, d_a,
+                       mid == 1 ? ap_value : nullptr, d_a, d_slot, 1, mid);
+    g_kernel_launches += 2;
+    if (mid > 1) {
+      hipLaunchKernelGGL(k_fold_scalars, dim3(blocks), dim3(256), 0, stream, d_b,
+                         static_cast<u8*>(nullptr), d_b, d_slot, 0, mid);
+      hipLaunchKernelGGL(k_fold_generators, dim3(blocks), dim3(256), 0, stream, d_g, d_terms, d_slot,
+                         d_q, mid);
+      g_kernel_launches += 2;
+    }
+    BZ_HIP_CHECK(hipGetLastError());
+  }
+}
+
+// the GPU backend's form on host operands: upload, the chain on the primary stream, download, one
+// synchronise
+void prove_uploaded(api_state& st, u8* l_vector, u8* r_vector, u8* ap_value, void* transcript, u64 n,
+                    u64 generators_offset, const u8* a_vector, const u8* b_vector) {
+  device_state& ds = st.primary();
+  ds.activate();
+  const u64 rounds = ceil_log2(n);
+  const workspace_layout layout{u64{1} << rounds};
+  ds.io.reset(2 * device_arena::padded(32 * n) + 2 * device_arena::padded(32 * rounds) +
+                  device_arena::padded(32) + device_arena::padded(sizeof(transcript_state)) +
+                  layout.total + 256,
+              ds.stream);
+  u8* d_a = ds.io.take<u8>(32 * n);
+  u8* d_b = ds.io.take<u8>(32 * n);
+  u8* d_l = ds.io.take<u8>(32 * rounds);
+  u8* d_r = ds.io.take<u8>(32 * rounds);
+  u8* d_ap = ds.io.take<u8>(32);
+  u8* d_transcript = ds.io.take<u8>(sizeof(transcript_state));
+  u8* d_workspace = ds.io.take<u8>(layout.total);
+  BZ_HIP_CHECK(hipMemcpyAsync(d_a, a_vector, 32 * n, hipMemcpyHostToDevice, ds.stream));
+  BZ_HIP_CHECK(hipMemcpyAsync(d_b, b_vector, 32 * n, hipMemcpyHostToDevice, ds.stream));
+  BZ_HIP_CHECK(hipMemcpyAsync(d_transcript, transcript, sizeof(transcript_state),
+                              hipMemcpyHostToDevice, ds.stream));
+  enqueue_chain(*ds.ctx, d_l, d_r, d_ap, d_transcript, n, generators_offset, nullptr, d_a, d_b,
+                d_workspace, layout.total, ds.stream);
+  BZ_HIP_CHECK(hipMemcpyAsync(l_vector, d_l, 32 * rounds, hipMemcpyDeviceToHost, ds.stream));
+  BZ_HIP_CHECK(hipMemcpyAsync(r_vector, d_r, 32 * rounds, hipMemcpyDeviceToHost, ds.stream));
+  BZ_HIP_CHECK(hipMemcpyAsync(ap_value, d_ap, 32, hipMemcpyDeviceToHost, ds.stream));
+  BZ_HIP_CHECK(hipMemcpyAsync(transcript, d_transcript, sizeof(transcript_state),
+                              hipMemcpyDeviceToHost, ds.stream));
+  BZ_HIP_CHECK(hipStreamSynchronize(ds.stream));
+}
+
+//--------------------------------------------------------------------------------------------------
+// the host backend's round loop (reference: prfip::cpu_driver, cpu_driver.cc)
+//--------------------------------------------------------------------------------------------------
+// current vector shapes: g has `size` entries, a and b have min(size, their original length) --
+// only round 0 can be ragged
 struct fold_shape {
   u64 size, a_len, b_len;
   u64 mid() const { return size / 2; }
@@ -164,14 +465,15 @@ struct fold_shape {
   }
 };
 
-class host_fold_backend final : public fold_backend {
+class host_fold_backend {
 public:
   host_fold_backend(api_state& st, u64 n, u64 np, u64 offset, const u8* a, const u8* b)
       : st_{st}, shape_{np, n, n}, a_(a, a + 32 * n), b_(b, b + 32 * n), g_(np) {
     host_builtin_generators_unlocked(st, g_.data(), np, offset);
   }
 
-  void commit_to_fold(u8 c_l[32], u8 c_r[32], ed_point& l_p, ed_point& r_p) override {
+  // c_l = <a_lo, b_hi>, c_r = <a_hi, b_lo> (canonical bytes); l_p = <a_lo, g_hi>, r_p = <a_hi, g_lo>
+  void commit_to_fold(u8 c_l[32], u8 c_r[32], ed_point& l_p, ed_point& r_p) {
     const u64 mid = shape_.mid();
     inner_product(c_l, a_.data(), b_.data() + 32 * mid, std::min(mid, shape_.b_len - mid));
     inner_product(c_r, a_.data() + 32 * mid, b_.data(), std::min(shape_.a_len - mid, mid));
@@ -179,7 +481,9 @@ public:
     r_p = msm(a_.data() + 32 * mid, shape_.a_len - mid, g_.data());
   }
 
-  void fold(const scalar& x, const scalar& x_inv) override {
+  // a' = x a_lo + x^-1 a_hi; unless one element is left: b' = x^-1 b_lo + x b_hi,
+  // g' = x^-1 g_lo + x g_hi
+  void fold(const scalar& x, const scalar& x_inv) {
     const u64 mid = shape_.mid();
     fold_scalars(a_, x, x_inv, mid, shape_.a_len);
     if (mid > 1) {
@@ -198,7 +502,7 @@ public:
     shape_.advance();
   }
 
-  void first_a(u8 out[32]) override { std::memcpy(out, a_.data(), 32); }
+  void first_a(u8 out[32]) { std::memcpy(out, a_.data(), 32); }
 
 private:
   api_state& st_;
@@ -232,146 +536,17 @@ private:
     return r;
   }
 };
-
-class device_fold_backend final : public fold_backend {
-public:
-  device_fold_backend(api_state& st, u64 n, u64 np, u64 offset, const u8* a, const u8* b)
-      : ds_{st.primary()}, shape_{np, n, n} {
-    ds_.activate();
-    const u64 mid = np / 2;
-    ds_.io.reset(2 * device_arena::padded(32 * n) + device_arena::padded(sizeof(ed_point) * np) +
-                     device_arena::padded(sizeof(ed29_cached_packed) * 3 * mid) +
-                     2 * device_arena::padded(sizeof(s25::fe) * kPartialBlocks) +
-                     device_arena::padded(2 * sizeof(ed_point)) + 4096,
-                 ds_.stream);
-    d_a_ = ds_.io.take<u64>(4 * n);
-    d_b_ = ds_.io.take<u64>(4 * n);
-    d_g_ = ds_.io.take<ed_point>(np);
-    d_terms_ = ds_.io.take<ed29_cached_packed>(3 * mid);
-    d_partials_ = ds_.io.take<s25::fe>(2 * kPartialBlocks);
-    d_msm_ = ds_.io.take<ed_point>(2);
-    BZ_HIP_CHECK(hipMemcpyAsync(d_a_, a, 32 * n, hipMemcpyHostToDevice, ds_.stream));
-    BZ_HIP_CHECK(hipMemcpyAsync(d_b_, b, 32 * n, hipMemcpyHostToDevice, ds_.stream));
-    builtin_generators_enqueue(d_g_, offset, np, ds_.stream);
-    g_kernel_launches += 1;
-  }
-
-  void commit_to_fold(u8 c_l[32], u8 c_r[32], ed_point& l_p, ed_point& r_p) override {
-    const u64 mid = shape_.mid();
-    const u64 n_l = std::min(mid, shape_.b_len - mid), n_r = std::min(shape_.a_len - mid, mid);
-    const u32 blocks_l = blocks_for(n_l), blocks_r = blocks_for(n_r);
-    if (n_l > 0) {
-      hipLaunchKernelGGL(k_inner_product, dim3(blocks_l), dim3(256), 0, ds_.stream, d_partials_,
-                         d_a_, d_b_ + 4 * mid, static_cast<u32>(n_l));
-    }
-    if (n_r > 0) {
-      hipLaunchKernelGGL(k_inner_product, dim3(blocks_r), dim3(256), 0, ds_.stream,
-                         d_partials_ + kPartialBlocks, d_a_ + 4 * mid, d_b_, static_cast<u32>(n_r));
-    }
-    BZ_HIP_CHECK(hipGetLastError());
-    g_kernel_launches += 2;
-    // the two MSMs of the round on the engine: generators and scalars already resident
-    const curve_vtable& vt = curve25519_vtable();
-    const std::vector<host_column> col_l{
-        byte_column(reinterpret_cast<const u8*>(d_a_), mid, 32, false)};
-    vt.msm(*ds_.ctx, reinterpret_cast<u8*>(d_msm_), sizeof(ed_point), true, col_l, nullptr,
-           d_g_ + mid, ds_.stream);
-    const std::vector<host_column> col_r{
-        byte_column(reinterpret_cast<const u8*>(d_a_ + 4 * mid), shape_.a_len - mid, 32, false)};
-    vt.msm(*ds_.ctx, reinterpret_cast<u8*>(d_msm_ + 1), sizeof(ed_point), true, col_r, nullptr,
-           d_g_, ds_.stream);
-    std::vector<s25::fe> partials(2 * kPartialBlocks);
-    ed_point results[2];
-    BZ_HIP_CHECK(hipMemcpyAsync(partials.data(), d_partials_, sizeof(s25::fe) * 2 * kPartialBlocks,
-                                hipMemcpyDeviceToHost, ds_.stream));
-    BZ_HIP_CHECK(hipMemcpyAsync(results, d_msm_, sizeof(results), hipMemcpyDeviceToHost,
-                                ds_.stream));
-    BZ_HIP_CHECK(hipStreamSynchronize(ds_.stream));
-    finish_inner_product(c_l, partials.data(), n_l > 0 ? blocks_l : 0);
-    finish_inner_product(c_r, partials.data() + kPartialBlocks, n_r > 0 ? blocks_r : 0);
-    l_p = results[0];
-    r_p = results[1];
-  }
-
-  void fold(const scalar& x, const scalar& x_inv) override {
-    const u32 mid = static_cast<u32>(shape_.mid());
-    const u32 blocks = (mid + 255) / 256;
-    hipLaunchKernelGGL(k_fold_scalars, dim3(blocks), dim3(256), 0, ds_.stream, d_a_, d_a_, x.m,
-                       x_inv.m, mid, static_cast<u32>(shape_.a_len));
-    g_kernel_launches += 1;
-    if (mid > 1) {
-      hipLaunchKernelGGL(k_fold_scalars, dim3(blocks), dim3(256), 0, ds_.stream, d_b_, d_b_,
-                         x_inv.m, x.m, mid, static_cast<u32>(shape_.b_len));
-      u8 lo[32], hi[32];
-      x_inv.to_bytes(lo);
-      x.to_bytes(hi);
-      const fold_digits digits = decompose_fold(lo, hi);
-      hipLaunchKernelGGL(k_fold_terms, dim3(blocks), dim3(256), 0, ds_.stream, d_terms_, d_g_, mid);
-      hipLaunchKernelGGL(k_fold_generators, dim3(blocks), dim3(256), 0, ds_.stream, d_g_, d_terms_,
-                         digits, mid);
-      g_kernel_launches += 3;
-    }
-    BZ_HIP_CHECK(hipGetLastError());
-    shape_.advance();
-  }
-
-  void first_a(u8 out[32]) override {
-    BZ_HIP_CHECK(hipMemcpyAsync(out, d_a_, 32, hipMemcpyDeviceToHost, ds_.stream));
-    BZ_HIP_CHECK(hipStreamSynchronize(ds_.stream));
-  }
-
-private:
-  static constexpr u32 kPartialBlocks = 256;
-  device_state& ds_;
-  fold_shape shape_;
-  u64* d_a_ = nullptr;
-  u64* d_b_ = nullptr;
-  ed_point* d_g_ = nullptr;
-  ed29_cached_packed* d_terms_ = nullptr;
-  s25::fe* d_partials_ = nullptr;
-  ed_point* d_msm_ = nullptr;
-
-  static u32 blocks_for(u64 count) {
-    return static_cast<u32>(std::min<u64>(kPartialBlocks, (count + 255) / 256));
-  }
-  static void finish_inner_product(u8 out[32], const s25::fe* partials, u32 blocks) {
-    s25::fe acc = s25::F::zero();
-    for (u32 k = 0; k < blocks; ++k) acc = s25::add(acc, partials[k]);
-    s25::store(out, s25::F::mul(acc, s25::r2()));
-  }
-};
-
-std::unique_ptr<fold_backend> make_backend(api_state& st, u64 n, u64 np, u64 offset, const u8* a,
-                                           const u8* b) {
-  if (st.backend == 2) return std::make_unique<device_fold_backend>(st, n, np, offset, a, b);
-  return std::make_unique<host_fold_backend>(st, n, np, offset, a, b);
-}
-
-u64 ceil_log2(u64 n) {
-  u64 k = 0;
-  while ((u64{1} << k) < n) ++k;
-  return k;
-}
-
-// proof_computation.cc:36-52
-void init_transcript(transcript& t, u64 n) {
-  t.set_domain("inner product proof v1");
-  t.append_u64("n", n);
-}
-scalar round_challenge(transcript& t, const u8* l_value, const u8* r_value) {
-  t.append_message("L", l_value, 32);
-  t.append_message("R", r_value, 32);
-  u8 x[32];
-  t.challenge_bytes(x, 32, "x");
-  return scalar::from_bytes(x); // == s25o::reduce32: every later use is modulo l
-}
 } // namespace
 
 void prove_inner_product(api_state& st, u8* l_vector, u8* r_vector, u8* ap_value,
                          void* transcript_bytes, u64 n, u64 generators_offset, const u8* a_vector,
                          const u8* b_vector) {
-  transcript t{transcript_bytes};
-  init_transcript(t, n);
+  if (st.backend == 2 && n > 1) {
+    prove_uploaded(st, l_vector, r_vector, ap_value, transcript_bytes, n, generators_offset, a_vector,
+                   b_vector);
+    return;
+  }
+  init_transcript<host_sponge>(static_cast<transcript_state*>(transcript_bytes), n);
   if (n == 1) {
     std::memcpy(ap_value, a_vector, 32); // verbatim, as proof_computation.cc:83-86
     return;
@@ -379,33 +554,47 @@ void prove_inner_product(api_state& st, u8* l_vector, u8* r_vector, u8* ap_value
   const u64 np = u64{1} << ceil_log2(n);
   ed_point q;
   host_builtin_generators_unlocked(st, &q, 1, generators_offset + np);
-  std::unique_ptr<fold_backend> backend =
-      make_backend(st, n, np, generators_offset, a_vector, b_vector);
+  host_fold_backend backend{st, n, np, generators_offset, a_vector, b_vector};
   u64 round = 0;
   for (u64 size = np; size > 1; size /= 2, ++round) {
     u8 c_l[32], c_r[32];
     ed_point l_p, r_p;
-    backend->commit_to_fold(c_l, c_r, l_p, r_p);
+    backend.commit_to_fold(c_l, c_r, l_p, r_p);
     l_p = ed::add(l_p, scalar_multiply(q, c_l));
     r_p = ed::add(r_p, scalar_multiply(q, c_r));
     u8* l_value = l_vector + 32 * round;
     u8* r_value = r_vector + 32 * round;
     ristretto::encode(l_value, l_p);
     ristretto::encode(r_value, r_p);
-    const scalar x = round_challenge(t, l_value, r_value);
-    backend->fold(x, x.inverse());
+    const scalar x = host_round_challenge(transcript_bytes, l_value, r_value);
+    backend.fold(x, x.inverse());
   }
-  backend->first_a(ap_value);
+  backend.first_a(ap_value);
+}
+
+u64 inner_product_workspace_bytes(u64 n) {
+  if (n == 0 || n > (u64{1} << 30)) return 0;
+  return workspace_layout{u64{1} << ceil_log2(n)}.total;
+}
+
+void prove_inner_product_device(msm_context& ctx, u8* l_vector, u8* r_vector, u8* ap_value,
+                                void* transcript, u64 n, u64 generators_offset,
+                                const void* generators, const u8* a_vector, const u8* b_vector,
+                                void* workspace, u64 workspace_bytes, hipStream_t stream) {
+  enqueue_chain(ctx, l_vector, r_vector, ap_value, static_cast<u8*>(transcript), n,
+                generators_offset, static_cast<const ed_point*>(generators), a_vector, b_vector,
+                workspace, workspace_bytes, stream);
 }
 
 bool verify_inner_product(api_state& st, void* transcript_bytes, u64 n, u64 generators_offset,
                           const u8* b_vector, const u8* product, const void* a_commit,
                           const u8* l_vector, const u8* r_vector, const u8* ap_value) {
   const u64 rounds = ceil_log2(n), np = u64{1} << rounds;
-  transcript t{transcript_bytes};
-  init_transcript(t, n);
+  init_transcript<host_sponge>(static_cast<transcript_state*>(transcript_bytes), n);
   std::vector<scalar> x(rounds);
-  for (u64 i = 0; i < rounds; ++i) x[i] = round_challenge(t, l_vector + 32 * i, r_vector + 32 * i);
+  for (u64 i = 0; i < rounds; ++i) {
+    x[i] = host_round_challenge(transcript_bytes, l_vector + 32 * i, r_vector + 32 * i);
+  }
 
   // exponents of [Q, g_0 .. g_{np-1}, L_0 .., R_0 ..] (verification_computation.cc:30-121)
   const u64 count = 1 + np + 2 * rounds;

@@ -197,6 +197,17 @@ struct wave_sponge {
     sync();
   }
 };
+
+// the caller's 203 bytes into / out of the LDS copy wavefront 0 works on
+BZ_DEV void wave_load_transcript(transcript_state& lds, const u8* transcript) {
+  u8* t = reinterpret_cast<u8*>(&lds);
+  for (u32 i = wave_sponge::lane(); i < sizeof(transcript_state); i += 64) t[i] = transcript[i];
+  wave_sponge::sync();
+}
+BZ_DEV void wave_store_transcript(u8* transcript, const transcript_state& lds) {
+  const u8* t = reinterpret_cast<const u8*>(&lds);
+  for (u32 i = wave_sponge::lane(); i < sizeof(transcript_state); i += 64) transcript[i] = t[i];
+}
 #endif
 
 // a label: characters and their number (device code has no std::string_view)

@@ -385,6 +385,31 @@ int bzamd_verify_sumcheck(void* expected_sum, void* evaluation_point, struct sxt
                           unsigned field_id, const void* round_polynomials, unsigned num_variables,
                           unsigned round_degree);
 
+/* The inner-product prover on device-resident vectors: sxt_curve25519_prove_inner_product as a
+ * chain of kernels that never returns to the host between rounds.  DEVICE pointers on the current
+ * HIP device: l_vector, r_vector (ceil_log2(n) x 32 bytes each; may be NULL for n = 1), ap_value
+ * (32 bytes), transcript (203 bytes, in / out, used in place), a_vector, b_vector (n x 32 bytes
+ * each, read in stream order, never written), generators (NULL: the built-in generators
+ * [generators_offset, generators_offset + np], derived on the device, Q = generator
+ * generators_offset + np, np = 2^ceil_log2(n); otherwise np + 1 sxt_ristretto255 elements, the
+ * last one Q, read only, and generators_offset is ignored) and workspace (at least
+ * bzamd_inner_product_workspace_bytes(n); less aborts).  gpu backend only.  The call only
+ * enqueues on `stream`: no synchronise, no callback, no allocation but the MSM engine's own
+ * buffers, which grow as for bzamd_msm_device; outputs, transcript and workspace are the caller's
+ * to reuse once the work enqueued by the call has completed, and a later call on the same stream
+ * may use the same workspace.  Same inputs, same bytes and transcript state as
+ * sxt_curve25519_prove_inner_product (n = 1: the transcript's init and ap = a[0] verbatim;
+ * unreduced scalars included); same limits and aborts (null arguments, n = 0, n > 2^30).
+ *
+ * bzamd_inner_product_workspace_bytes depends on np alone, needs no backend, and returns 0 for
+ * n = 0 and n > 2^30. */
+uint64_t bzamd_inner_product_workspace_bytes(uint64_t n);
+void bzamd_prove_inner_product_device(void* l_vector, void* r_vector, void* ap_value,
+                                      void* transcript, uint64_t n, uint64_t generators_offset,
+                                      const void* generators, const void* a_vector,
+                                      const void* b_vector, void* workspace,
+                                      uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
