@@ -12,6 +12,8 @@ translation unit that instantiates the code, taken from blitzar_amd.build (never
     ed_niels         msm/msm_curve25519_niels_accumulate.hip     f29, the Z = 1 addition forms of ed29
     <curve>          msm/msm_<curve>.hip                         mont29, sw29, sww::wave, add_coop4
     <curve>_acc      msm/msm_<curve>_accumulate.hip              mont29, sw29 (add_mixed_acc's flag set)
+    proof            proof/sumcheck_transcript.hip               wave_sponge, Merlin, scalar25, the element
+                                                                 conversions, the protocol steps of the provers
 
 BZ_DEVICE_HOOKS_LIB=<path> loads another build of the library instead (a harness compiled from a
 modified copy of the headers: how one shows that the tests notice a wrong kernel)."""
@@ -35,7 +37,8 @@ CURVES = {"bn254": ("bn254_msm", "bn254_g1_29"), "grumpkin": ("grumpkin_msm", "g
 def objects():
     """tag -> (product translation unit whose flags it takes, defines)"""
     objs = {"ed": ("msm/msm_curve25519.hip", ["-DBZ_DH_ED=1", "-DBZ_DH_ED_WAVE=1"]),
-            "ed_niels": ("msm/msm_curve25519_niels_accumulate.hip", ["-DBZ_DH_ED=1", "-DBZ_DH_ED_NIELS=1"])}
+            "ed_niels": ("msm/msm_curve25519_niels_accumulate.hip", ["-DBZ_DH_ED=1", "-DBZ_DH_ED_NIELS=1"]),
+            "proof": ("proof/sumcheck_transcript.hip", ["-DBZ_DH_PROOF=1"])}
     for name, (trait, curve) in CURVES.items():
         defs = [f"-DBZ_DH_SW={trait}", f"-DBZ_DH_G={curve}"]
         if name == "bls12_381":
@@ -116,3 +119,43 @@ def run(tag, op, inputs, out_words, params=()):
         what = {-1: "unknown op", -2: "record sizes do not match the op", -3: "parameters out of range"}
         raise HarnessError(f"{tag}/{op}: {what.get(rc, 'HIP error %d' % rc)}")
     return out
+
+
+def assert_proof_rejections():
+    """what the `proof` object cannot validate it rejects on the host, before anything is launched:
+    the record fields a kernel would index memory with, and parameters out of range"""
+    rate, scalar_bits = 166, 253        # kRate of proof/transcript.h, kScalarBits of proof/inner_product_protocol.h
+
+    def refused(what, op, record_words, out_words, params=(), byte=None, value=0):
+        rec = np.zeros((2, record_words), np.uint32)      # (the second record is the offending one)
+        if byte is not None:
+            rec[1].view(np.uint8)[byte] = value
+        try:
+            run("proof", op, rec, out_words, params)
+        except HarnessError as e:
+            assert what in str(e), (op, params, byte, value, str(e))
+        else:
+            raise AssertionError(f"proof/{op} accepted params {params}, byte {byte} = {value}")
+
+    # a transcript's position indexes LDS
+    for pos in (rate, rate + 1, 255):
+        refused("parameters out of range", "merlin_wave", 183, 115, (1, 0, 32, 0), 200, pos)
+        refused("parameters out of range", "sumcheck_round_wave", 123, 75, (0, 2), 200, pos)
+        refused("parameters out of range", "ip_round_wave", 69, 67, (0,), 200, pos)
+    # digits pick one of three terms, the count (the word behind the 256 digits) bounds the walk
+    for byte, value in ((0, 4), (255, 0xff), (256, scalar_bits + 1), (259, 1)):
+        refused("parameters out of range", "ip_fold_point", 145, 40, (), byte, value)
+    # parameter ranges
+    for params in ((0,), (3,)):
+        refused("parameters out of range", "keccak_wave", 50, 50, params)
+    for params in ((0, 0, 32, 0), (17, 0, 32, 0), (1, 513, 32, 0), (1, 0, 0, 0), (1, 0, 257, 0),
+                   (1, 8, 32, 2), (1, 7, 32, 1)):
+        refused("parameters out of range", "merlin_wave", 183, 115, params)
+    for n in (0, 65):
+        refused("parameters out of range", "s25_dot", 16 * n, 8, (n,))
+    for params in ((2, 2), (0, 1), (0, 10)):
+        refused("parameters out of range", "sumcheck_round_wave", 123, 75, params)
+    refused("parameters out of range", "ip_round_wave", 69, 67, (2,))
+    # sizes that do not match the op's record, and an op of another object
+    refused("record sizes", "merlin_wave", 182, 115, (1, 0, 32, 0))
+    refused("unknown op", "f29_mul", 18, 9)

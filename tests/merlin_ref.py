@@ -176,3 +176,96 @@ def sumcheck_callback(t, field_id):
         r = sumcheck_round(t, field_id, ctypes.string_at(poly_ptr, 32 * length))
         ctypes.memmove(r_ptr, r, 32)
     return cb
+
+
+#--------------------------------------------------------------------------------------------------
+# the model instrumented: which edges of the 166-byte rate boundary a sequence of operations reaches
+#--------------------------------------------------------------------------------------------------
+# the sponge fills up (position RATE, a permutation) inside a run of bytes or on its last byte, per
+# kind of run: the 2-byte header of an operation, a label, the 4-byte length, a message
+ABSORB_CLASSES = frozenset(f"{kind}-{where}" for kind in ("header", "label", "length", "message")
+                           for where in ("inside", "last"))
+# a prf whose header leaves the position off / on the boundary: begin_op forces a permutation / must not
+PRF_CLASSES = frozenset(("prf-forced", "prf-unforced"))
+BOUNDARY_CLASSES = ABSORB_CLASSES | PRF_CLASSES          # what 32-byte challenges can reach
+SQUEEZE_CROSS = "squeeze-cross"                           # a squeeze that goes on across the boundary
+
+
+class TracedTranscript(Transcript):
+    """Transcript that records in `classes` the boundary classes its operations reached and in
+    `starts` the position every operation began at"""
+
+    def __init__(self, raw=None, label=None):
+        self.classes, self.starts, self._kind = set(), [], "label"
+        super().__init__(raw, label)
+
+    def _absorb(self, data):
+        s = self.raw
+        for i, byte in enumerate(data):
+            s[s[200]] ^= byte
+            s[200] += 1
+            if s[200] == RATE:
+                self._run_f()
+                self.classes.add(f"{self._kind}-{'last' if i + 1 == len(data) else 'inside'}")
+
+    def _squeeze(self, n):
+        s, out = self.raw, bytearray()
+        for i in range(n):
+            out.append(s[s[200]])
+            s[s[200]] = 0
+            s[200] += 1
+            if s[200] == RATE:
+                self._run_f()
+                if i + 1 < n:
+                    self.classes.add(SQUEEZE_CROSS)
+        return bytes(out)
+
+    def _begin_op(self, flags, more):
+        if more:
+            return
+        s = self.raw
+        self.starts.append(s[200])
+        old_begin = s[201]
+        s[201] = (s[200] + 1) & 0xff
+        s[202] = flags
+        kind, self._kind = self._kind, "header"
+        self._absorb(bytes([old_begin, flags]))
+        self._kind = kind
+        if flags & (FLAG_C | FLAG_K):
+            if s[200] != 0:
+                self._run_f()
+                self.classes.add("prf-forced")
+            else:
+                self.classes.add("prf-unforced")
+
+    def _meta_ad(self, data, more):
+        self._kind = "length" if more else "label"
+        super()._meta_ad(data, more)
+
+    def _ad(self, data, more):
+        self._kind = "message"
+        super()._ad(data, more)
+
+
+def padded_starts(label=b"sweep"):
+    """166 transcripts, the k-th at STROBE position k: a fresh transcript and one padding message of
+    0 .. 165 bytes (each more byte moves the position on by one, modulo the rate)"""
+    starts = {}
+    for k in range(RATE):
+        t = Transcript(label=label)
+        t.append_message(b"pad", bytes(k))
+        starts[t.raw[200]] = t.array()
+    assert sorted(starts) == list(range(RATE)), "the padded transcripts miss a position"
+    return [starts[k] for k in range(RATE)]
+
+
+def inner_product_begin(t, n):
+    t.append_message(b"domain-sep", b"inner product proof v1")
+    t.append_u64(b"n", n)
+
+
+def inner_product_round(t, l_value, r_value):
+    """-> the 32 squeezed bytes x (the challenge is the integer x mod l)"""
+    t.append_message(b"L", l_value)
+    t.append_message(b"R", r_value)
+    return t.challenge_bytes(b"x", 32)

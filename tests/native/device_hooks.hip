@@ -11,6 +11,10 @@
 //     -DBZ_DH_ED_WAVE=1 / -DBZ_DH_SW_WAVE=1   also the wave ops (ed16w, sww::wave, add_coop4, the traits'
 //                             wave members), in the object built like the TU that instantiates them
 //     -DBZ_DH_SW_BLS=1        bls12-381: the define its product translation units set
+//     -DBZ_DH_PROOF=1         the proof kernels' pieces: the wavefront's Keccak / Merlin of
+//                             proof/transcript.h, the scalar arithmetic of proof/scalar25.h and the element
+//                             conversions of proof/sumcheck_rows.h as the kernels use them, and the protocol
+//                             steps of proof/sumcheck_protocol.h and proof/inner_product_protocol.h
 // and the objects are linked into tests/native/_build/libbz_device_hooks.so.  Not part of
 // libblitzar_amd.so.
 //
@@ -18,7 +22,9 @@
 // with host pointers; it allocates, copies, launches, synchronises and returns the HIP status
 // (negative: -1 unknown op, -2 sizes do not match the op's record layout, -3 parameters out of range).
 // Every case is one fixed-size record of 32-bit words; record sizes depend on the op and on the
-// validated `params` only, never on the data, and no kernel forms an address from input data.
+// validated `params` only, never on the data, and no kernel forms an address from input data: the
+// few record fields that index memory (a transcript's position, fold digits and their count) are
+// checked on the host before the launch (-3) and clamped in the kernel.
 //   per-lane ops: one case per thread, blocks of 64
 //   wave ops:     one case per 64-thread workgroup, with the product's wave_scratch()
 #if defined(BZ_DH_SW_BLS)
@@ -29,6 +35,13 @@
 #include <cstring>
 
 #include "blitzar_amd/csrc/msm/curve_traits.h"
+#if defined(BZ_DH_PROOF)
+#include "blitzar_amd/csrc/proof/inner_product_protocol.h"
+#include "blitzar_amd/csrc/proof/scalar25.h"
+#include "blitzar_amd/csrc/proof/sumcheck_protocol.h"
+#include "blitzar_amd/csrc/proof/sumcheck_rows.h"
+#include "blitzar_amd/csrc/proof/transcript.h"
+#endif
 
 #define BZ_DH_CAT2(a, b) a##b
 #define BZ_DH_CAT(a, b) BZ_DH_CAT2(a, b)
@@ -73,13 +86,16 @@ template <class Op> __global__ void __launch_bounds__(64) k_wave(const u32* in, 
           pr);
 }
 
+// valid_records: the record fields a kernel indexes memory with, checked before the launch
 struct op_base {
   static constexpr bool wave = false;
   static bool valid(const params4&) { return true; }
+  static bool valid_records(const u32*, u32, const params4&) { return true; }
 };
 struct wave_op_base {
   static constexpr bool wave = true;
   static bool valid(const params4&) { return true; }
+  static bool valid_records(const u32*, u32, const params4&) { return true; }
 };
 #define BZ_DH_IO(IN, OUT)                                                                          \
   __host__ __device__ static constexpr u32 in_words(const params4&) { return IN; }                 \
@@ -647,12 +663,290 @@ struct sw29_coop4 : wave_op_base {
 #endif
 #endif // BZ_DH_SW
 
+#if defined(BZ_DH_PROOF)
+//--------------------------------------------------------------------------------------------------
+// proof/: the wavefront's sponge and Merlin, one case per workgroup of 64 with the state in LDS as
+// the product kernels hold it (8-byte aligned); the scalar and element arithmetic, one case per
+// lane, each op the expression a product kernel evaluates
+//--------------------------------------------------------------------------------------------------
+using namespace proof;
+using sponge_strobe = strobe128_over<wave_sponge>;
+constexpr u32 kRate = sponge_strobe::kRate;
+constexpr u32 kTr = 51 /* the 203 bytes of a transcript and one of padding */, kS = 8 /* 32 bytes */;
+constexpr u32 kMaxLabel = 16, kMaxMessage = 512, kMaxChallenge = 256;
+
+__device__ __forceinline__ void wave_copy_in(u8* lds, const u32* in, u32 bytes) {
+  const u8* b = reinterpret_cast<const u8*>(in);
+  for (u32 i = wave_sponge::lane(); i < bytes; i += 64) lds[i] = b[i];
+}
+__device__ __forceinline__ void wave_copy_out(u32* out, const u8* lds, u32 bytes) {
+  u8* b = reinterpret_cast<u8*>(out);
+  for (u32 i = wave_sponge::lane(); i < bytes; i += 64) b[i] = lds[i];
+}
+// the caller's transcript into LDS; `pos` indexes the state: validated on the host, clamped here
+__device__ __forceinline__ void load_checked_transcript(transcript_state& t, const u32* in) {
+  wave_load_transcript(t, reinterpret_cast<const u8*>(in));
+  if (wave_sponge::lane() == 0 && t.pos >= kRate) t.pos = kRate - 1;
+  wave_sponge::sync();
+}
+// every record starts with a transcript: pos < kRate
+template <class Op> bool transcripts_valid(const u32* in, u32 cases, const params4& pr) {
+  for (u32 c = 0; c < cases; ++c) {
+    const u8* t = reinterpret_cast<const u8*>(in + static_cast<size_t>(c) * Op::in_words(pr));
+    if (t[200] >= kRate) return false;
+  }
+  return true;
+}
+
+// params: {permutations 1 .. 2}; record: 200 state bytes -> 200 state bytes
+struct keccak_wave : wave_op_base {
+  static bool valid(const params4& p) { return p.v[0] >= 1 && p.v[0] <= 2; }
+  BZ_DH_IO(50, 50)
+  __device__ static void run(const u32* in, u32* out, const params4& pr) {
+    __shared__ alignas(8) u8 state[200];
+    wave_copy_in(state, in, 200);
+    wave_sponge::sync();
+    wave_sponge::permute(state);
+    if (pr.v[0] >= 2) wave_sponge::permute(state);
+    wave_copy_out(out, state, 200);
+  }
+};
+// params: {label bytes 1 .. 16, message bytes 0 .. 512, challenge bytes 1 .. 256, form};
+// record: transcript, label, message -> transcript, challenge.  form 0: append_message(label,
+// message), form 1 (message bytes = 8): append_u64(label, the message's 8 bytes as an integer);
+// then challenge_bytes(label)
+struct merlin_wave : wave_op_base {
+  static bool valid(const params4& p) {
+    return p.v[0] >= 1 && p.v[0] <= kMaxLabel && p.v[1] <= kMaxMessage && p.v[2] >= 1 &&
+           p.v[2] <= kMaxChallenge && (p.v[3] == 0 || (p.v[3] == 1 && p.v[1] == 8));
+  }
+  static bool valid_records(const u32* in, u32 cases, const params4& pr) {
+    return transcripts_valid<merlin_wave>(in, cases, pr);
+  }
+  BZ_DH_IO(kTr + kMaxLabel / 4 + kMaxMessage / 4, kTr + kMaxChallenge / 4)
+  struct alignas(8) lds_state {
+    transcript_state t;
+    u8 pad[5];
+    u8 message[kMaxMessage];
+    u8 challenge[kMaxChallenge];
+    char name[kMaxLabel];
+  };
+  __device__ static void run(const u32* in, u32* out, const params4& pr) {
+    __shared__ lds_state w;
+    const u32 label_bytes = pr.v[0] > kMaxLabel ? kMaxLabel : pr.v[0];
+    const u32 message_bytes = pr.v[1] > kMaxMessage ? kMaxMessage : pr.v[1];
+    const u32 challenge_bytes = pr.v[2] > kMaxChallenge ? kMaxChallenge : pr.v[2];
+    load_checked_transcript(w.t, in);
+    wave_copy_in(reinterpret_cast<u8*>(w.name), in + kTr, kMaxLabel);
+    wave_copy_in(w.message, in + kTr + kMaxLabel / 4, kMaxMessage);
+    wave_sponge::sync();
+    const label_view name{w.name, label_bytes};
+    transcript_over<wave_sponge> tr{&w.t};
+    if (pr.v[3] == 0) {
+      tr.append_message(name, w.message, message_bytes);
+    } else {
+      const u32* m = in + kTr + kMaxLabel / 4;
+      tr.append_u64(name, m[0] | (static_cast<u64>(m[1]) << 32));
+    }
+    tr.challenge_bytes(w.challenge, challenge_bytes, name);
+    wave_store_transcript(reinterpret_cast<u8*>(out), w.t);
+    wave_copy_out(out + kTr, w.challenge, challenge_bytes);
+  }
+};
+
+__device__ __forceinline__ const u8* bytes_of(const u32* in) { return reinterpret_cast<const u8*>(in); }
+__device__ __forceinline__ u8* bytes_of(u32* out) { return reinterpret_cast<u8*>(out); }
+
+// round_challenge and the scalar challenge::make: any 256-bit integer to its canonical residue
+struct s25_reduce : op_base {
+  BZ_DH_IO(kS, kS)
+  __device__ static void run(const u32* in, u32* out, const params4&) {
+    s25::store(bytes_of(out), s25::from_mont(s25::to_mont(s25::load(bytes_of(in)))));
+  }
+};
+// k_fold_scalars; record: m_low, m_high, u, v
+struct s25_fold : op_base {
+  BZ_DH_IO(4 * kS, kS)
+  __device__ static void run(const u32* in, u32* out, const params4&) {
+    const s25::fe m_low = s25::to_mont(s25::load(bytes_of(in)));
+    const s25::fe m_high = s25::to_mont(s25::load(bytes_of(in + kS)));
+    s25::store(bytes_of(out), s25::add(s25::F::mul(m_low, s25::load(bytes_of(in + 2 * kS))),
+                                       s25::F::mul(m_high, s25::load(bytes_of(in + 3 * kS)))));
+  }
+};
+// k_inner_product with k_cross_finish; params: {n 1 .. 64}; record: n x (a_i, b_i)
+struct s25_dot : op_base {
+  static bool valid(const params4& p) { return p.v[0] >= 1 && p.v[0] <= 64; }
+  __host__ __device__ static constexpr u32 in_words(const params4& p) { return p.v[0] * 2 * kS; }
+  __host__ __device__ static constexpr u32 out_words(const params4&) { return kS; }
+  __device__ static void run(const u32* in, u32* out, const params4& pr) {
+    const u32 n = pr.v[0] > 64 ? 64 : pr.v[0];
+    s25::fe acc = s25::F::zero();
+    for (u32 i = 0; i < n; ++i) {
+      acc = s25::add(acc, s25::F::mul(s25::load(bytes_of(in + 2 * kS * i)),
+                                      s25::load(bytes_of(in + 2 * kS * i + kS))));
+    }
+    s25::store(bytes_of(out), s25::F::mul(acc, s25::r2()));
+  }
+};
+// k_round_challenge's 1 / x (zero for zero)
+struct s25_invert : op_base {
+  BZ_DH_IO(kS, kS)
+  __device__ static void run(const u32* in, u32* out, const params4&) {
+    s25::store(bytes_of(out), s25::from_mont(s25::F::invert(s25::to_mont(s25::load(bytes_of(in))))));
+  }
+};
+// the element conversions of proof/sumcheck_rows.h, E = scalar25519_elements (sc_) / grumpkin_elements (gk_)
+template <class E> struct el_roundtrip : op_base {
+  BZ_DH_IO(kS, kS)
+  __device__ static void run(const u32* in, u32* out, const params4&) {
+    E::store(bytes_of(out), E::load(bytes_of(in)));
+  }
+};
+// record: four 64-bit words, element
+template <class E> struct el_convert : op_base {
+  BZ_DH_IO(kS + 1, kS)
+  __device__ static void run(const u32* in, u32* out, const params4&) {
+    u64 w[4];
+    for (int i = 0; i < 4; ++i) w[i] = in[2 * i] | (static_cast<u64>(in[2 * i + 1]) << 32);
+    E::store(bytes_of(out), E::convert(w, in[kS] != 0));
+  }
+};
+// wave_round's 1 - r
+template <class E> struct el_one_minus : op_base {
+  BZ_DH_IO(kS, kS)
+  __device__ static void run(const u32* in, u32* out, const params4&) {
+    using F = typename E::F;
+    E::store(bytes_of(out), fsub<F>(F::one(), E::load(bytes_of(in))));
+  }
+};
+// record: x -> r_bytes, E::store of the returned engine form
+template <class E> struct el_challenge_make : op_base {
+  BZ_DH_IO(kS, 2 * kS)
+  __device__ static void run(const u32* in, u32* out, const params4&) {
+    const typename E::F::fe r = challenge<E>::make(bytes_of(out), bytes_of(in));
+    E::store(bytes_of(out + kS), r);
+  }
+};
+struct sc_roundtrip : el_roundtrip<scalar25519_elements> {};
+struct gk_roundtrip : el_roundtrip<grumpkin_elements> {};
+struct sc_convert : el_convert<scalar25519_elements> {};
+struct gk_convert : el_convert<grumpkin_elements> {};
+struct sc_one_minus : el_one_minus<scalar25519_elements> {};
+struct gk_one_minus : el_one_minus<grumpkin_elements> {};
+struct sc_challenge_make : el_challenge_make<scalar25519_elements> {};
+struct gk_challenge_make : el_challenge_make<grumpkin_elements> {};
+
+// params: {field_id 0 .. 1, length 2 .. 9}; record: transcript, polynomial (9 x 32 bytes) ->
+// transcript, x, r in the caller's representation, E::store of the returned engine form
+struct sumcheck_round_wave : wave_op_base {
+  static bool valid(const params4& p) { return p.v[0] <= 1 && p.v[1] >= 2 && p.v[1] <= kMaxDegree + 1; }
+  static bool valid_records(const u32* in, u32 cases, const params4& pr) {
+    return transcripts_valid<sumcheck_round_wave>(in, cases, pr);
+  }
+  BZ_DH_IO(kTr + (kMaxDegree + 1) * kS, kTr + 3 * kS)
+  struct alignas(8) lds_state { // proof/sumcheck_transcript.hip wave_transcript
+    transcript_state t;
+    u8 pad[5];
+    u8 message[(kMaxDegree + 1) * 32];
+    u8 x[32], r[32], engine[32];
+  };
+  template <class E> __device__ static void round(lds_state& w, u32 length) {
+    const typename E::F::fe r = transcript_round<E, wave_sponge>(w.r, w.x, &w.t, w.message, length);
+    wave_sponge::sync();
+    if (wave_sponge::lane() == 0) E::store(w.engine, r);
+    wave_sponge::sync();
+  }
+  __device__ static void run(const u32* in, u32* out, const params4& pr) {
+    __shared__ lds_state w;
+    const u32 length = pr.v[1] > kMaxDegree + 1 ? kMaxDegree + 1 : pr.v[1];
+    load_checked_transcript(w.t, in);
+    wave_copy_in(w.message, in + kTr, (kMaxDegree + 1) * 32);
+    wave_sponge::sync();
+    if (pr.v[0] == 0) {
+      round<scalar25519_elements>(w, length);
+    } else {
+      round<grumpkin_elements>(w, length);
+    }
+    wave_store_transcript(bytes_of(out), w.t);
+    wave_copy_out(out + kTr, w.x, 32);
+    wave_copy_out(out + kTr + kS, w.r, 32);
+    wave_copy_out(out + kTr + 2 * kS, w.engine, 32);
+  }
+};
+// k_round_challenge's transcript step; params: {init 0 .. 1}; record: transcript, L, R, n (64 bits)
+// -> transcript, x, the returned x mod l as store(from_mont(.))
+struct ip_round_wave : wave_op_base {
+  static bool valid(const params4& p) { return p.v[0] <= 1; }
+  static bool valid_records(const u32* in, u32 cases, const params4& pr) {
+    return transcripts_valid<ip_round_wave>(in, cases, pr);
+  }
+  BZ_DH_IO(kTr + 2 * kS + 2, kTr + 2 * kS)
+  struct alignas(8) lds_state { // proof/inner_product.hip wave_state
+    transcript_state t;
+    u8 pad[5];
+    u8 l[32], r[32], x[32], reduced[32];
+  };
+  __device__ static void run(const u32* in, u32* out, const params4& pr) {
+    __shared__ lds_state w;
+    load_checked_transcript(w.t, in);
+    wave_copy_in(w.l, in + kTr, 32);
+    wave_copy_in(w.r, in + kTr + kS, 32);
+    wave_sponge::sync();
+    const u64 n = in[kTr + 2 * kS] | (static_cast<u64>(in[kTr + 2 * kS + 1]) << 32);
+    if (pr.v[0] != 0) init_transcript<wave_sponge>(&w.t, n);
+    const s25::fe x = round_challenge<wave_sponge>(w.x, &w.t, w.l, w.r);
+    wave_sponge::sync();
+    if (wave_sponge::lane() == 0) s25::store(w.reduced, s25::from_mont(x));
+    wave_sponge::sync();
+    wave_store_transcript(bytes_of(out), w.t);
+    wave_copy_out(out + kTr, w.x, 32);
+    wave_copy_out(out + kTr + kS, w.reduced, 32);
+  }
+};
+// a lane of k_fold_generators over the terms of k_fold_terms; record: 256 digit bytes, count, g_lo,
+// g_hi (ed_point) -> m_low g_lo + m_high g_hi (ed_point).  Digits pick one of three terms and the
+// count bounds the walk: at most 3 and kScalarBits, validated on the host, clamped here
+struct ip_fold_point : op_base {
+  static constexpr u32 kEdPoint = 40;
+  BZ_DH_IO(65 + 2 * kEdPoint, kEdPoint)
+  static bool valid_records(const u32* in, u32 cases, const params4& pr) {
+    for (u32 c = 0; c < cases; ++c) {
+      const u32* rec = in + static_cast<size_t>(c) * in_words(pr);
+      if (rec[64] > kScalarBits) return false;
+      const u8* d = reinterpret_cast<const u8*>(rec);
+      for (u32 i = 0; i < 256; ++i) {
+        if (d[i] > 3) return false;
+      }
+    }
+    return true;
+  }
+  __device__ static void run(const u32* in, u32* out, const params4&) {
+    fold_digits digits;
+    for (u32 i = 0; i < 256; ++i) digits.d[i] = bytes_of(in)[i] & 3;
+    digits.count = in[64] > kScalarBits ? kScalarBits : in[64];
+    const ed29_point lo = ed29::from_ed(load_as<ed_point>(in + 65));
+    const ed29_point hi = ed29::from_ed(load_as<ed_point>(in + 65 + kEdPoint));
+    const ed29_cached_packed terms[3] = {ed29::pack(ed29::to_cached(lo)), ed29::pack(ed29::to_cached(hi)),
+                                         ed29::pack(ed29::to_cached(ed29::add(lo, hi)))};
+    const ed29_point r = fold_point(digits, [&](u32 k) { return ed29::unpack(terms[k > 2 ? 2 : k]); });
+    store_as(out, ed29::to_ed(r));
+  }
+};
+
+#define BZ_DH_OPS(X)                                                                               \
+  X(keccak_wave) X(merlin_wave) X(s25_reduce) X(s25_fold) X(s25_dot) X(s25_invert)                 \
+  X(sc_roundtrip) X(gk_roundtrip) X(sc_convert) X(gk_convert) X(sc_one_minus) X(gk_one_minus)      \
+  X(sc_challenge_make) X(gk_challenge_make) X(sumcheck_round_wave) X(ip_round_wave) X(ip_fold_point)
+#endif // BZ_DH_PROOF
+
 template <class Op>
 int launch(const u32* in, u64 in_words, u32* out, u64 out_words, u32 cases, const params4& pr) {
   if (!Op::valid(pr)) return -3;
   if (cases == 0 || cases > kMaxCases) return -3;
   if (in_words != static_cast<u64>(cases) * Op::in_words(pr)) return -2;
   if (out_words != static_cast<u64>(cases) * Op::out_words(pr)) return -2;
+  if (!Op::valid_records(in, cases, pr)) return -3;
   u32 *din = nullptr, *dout = nullptr;
   hipError_t e = hipMalloc(&din, in_words * 4);
   if (e != hipSuccess) return static_cast<int>(e);

@@ -75,6 +75,26 @@ def ed_mul(k, a):
     return acc
 
 
+def ed_ext_add(a, b):
+    """extended twisted-Edwards addition (a = -1) on (X, Y, Z, T): complete, no inversion"""
+    x1, y1, z1, t1 = a
+    x2, y2, z2, t2 = b
+    aa, bb = (y1 - x1) * (y2 - x2) % P, (y1 + x1) * (y2 + x2) % P
+    cc, dd = 2 * D * t1 * t2 % P, 2 * z1 * z2 % P
+    e, f, g, h = bb - aa, dd - cc, dd + cc, bb + aa
+    return (e * f % P, g * h % P, f * g % P, e * h % P)
+
+
+def ed_ext_mul(k, pt):
+    """k pt in extended coordinates, by double-and-add without inversions (pt affine)"""
+    acc, ext = (0, 1, 1, 0), (pt[0], pt[1], 1, pt[0] * pt[1] % P)
+    for bit in bin(k)[2:] if k else "":
+        acc = ed_ext_add(acc, acc)
+        if bit == "1":
+            acc = ed_ext_add(acc, ext)
+    return acc
+
+
 def ed_multiples(n, first=1, step=1):
     """[first B, (first + step) B, ...], n points"""
     out, cur, inc = [], ed_mul(first, ED_BASE), ed_mul(step, ED_BASE)

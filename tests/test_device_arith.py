@@ -712,3 +712,5 @@ def test_harness_rejects_what_it_cannot_validate():
         dh.run("ed", "ed16w_fmul", u32([[0] * 127]), 64)
     with pytest.raises(dh.HarnessError):
         dh.run("ed", "ed_wave_horner", u32([[0] * (19 * 36)]), 36, (18, 16, 1))
+    # the proof object: a transcript position, fold digits and their count, parameter ranges
+    dh.assert_proof_rejections()

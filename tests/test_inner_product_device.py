@@ -2,13 +2,15 @@
 bzamd_inner_product_workspace_bytes, bzamd_prove_inner_product_device) against the reference's own
 prover (oracle.ip_prove): L, R, the final scalar and the 203 bytes of the transcript after the
 proof are byte-identical, for the built-in generators and for caller-supplied resident ones, for
-proofs enqueued back to back on one stream, and for unreduced input scalars."""
+proofs enqueued back to back on one stream, for unreduced input scalars, and from a caller's
+transcript at every position of the sponge."""
 import ctypes
 
 import numpy as np
 import pytest
 
 from blitzar_amd import api
+from tests import merlin_ref
 from tests.golden.make_golden_inner_product import GOLDEN, golden_inputs
 from tests.test_inner_product import scalars
 
@@ -176,6 +178,57 @@ def test_back_to_back(gpu_backend, oracle):
     assert_proof_equal(proofs[2].results(), want[2])
     # the first proof's transcript went on into the third
     assert_proof_equal(proofs[0].results()[:3], want[0][:3])
+
+
+def sponge_model(t0, n, l_values=None, r_values=None):
+    """the instrumented Python transcript through a proof of n elements from t0; L and R (zeros when
+    not given: which edges of the rate boundary are reached depends on lengths alone)"""
+    t = merlin_ref.TracedTranscript(raw=t0)
+    merlin_ref.inner_product_begin(t, n)
+    for i in range(rounds_of(n)):
+        merlin_ref.inner_product_round(t, bytes(32) if l_values is None else l_values[i].tobytes(),
+                                       bytes(32) if r_values is None else r_values[i].tobytes())
+    return t
+
+
+def single_element_positions():
+    """n = 1 is the transcript's init alone: the positions from which it fills the sponge, and two
+    from which it does not"""
+    starts = merlin_ref.padded_starts()
+    return sorted({0, 108} | {pos for pos in range(merlin_ref.RATE) if sponge_model(starts[pos], 1).classes})
+
+
+def test_sponge_sweep_reaches_every_boundary_class():
+    """a caller who continues a transcript hands the prover any of the 166 positions: the smallest
+    proof with a round (n = 2), from each, crosses the rate boundary in every way a 32-byte
+    challenge can"""
+    starts = merlin_ref.padded_starts()
+    reached = set()
+    for t0 in starts:
+        reached |= sponge_model(t0, 2).classes
+    assert reached == merlin_ref.BOUNDARY_CLASSES, sorted(merlin_ref.BOUNDARY_CLASSES - reached)
+    assert {0, 108, 109, 164, 165} <= set(single_element_positions())
+
+
+@pytest.mark.gpu
+def test_device_form_at_every_sponge_position(gpu_backend, oracle):
+    """n = 2 (k_round_challenge and one round) from every position, n = 1 (k_single_element) from the
+    positions at which the init fills the sponge.  The transcript is compared with the Python model
+    fed the device's own L and R first: a difference there is the sponge's, not the MSM's."""
+    starts = merlin_ref.padded_starts()
+    rng = np.random.default_rng(2800)
+    reached = set()
+    for n, positions in ((2, range(merlin_ref.RATE)), (1, single_element_positions())):
+        for pos in positions:
+            a, b = scalars(rng, n), scalars(rng, n)
+            got, _ = prove_on_device(gpu_backend, n, 0, a, b, starts[pos])
+            model = sponge_model(starts[pos], n, got[0], got[1])
+            assert np.array_equal(got[3], model.array()), f"n = {n}, position {pos}: the transcript differs"
+            for name, g, w in zip(("L", "R", "ap", "transcript"), got, oracle.ip_prove(starts[pos], n, 0, a, b)):
+                assert np.array_equal(g, w), f"n = {n}, position {pos}: {name} differs"
+            if n == 2:
+                reached |= model.classes
+    assert reached == merlin_ref.BOUNDARY_CLASSES
 
 
 @pytest.mark.gpu

@@ -18,7 +18,7 @@ import pytest
 from blitzar_amd import api
 from tests import merlin_ref
 from tests.test_sumcheck import CASES
-from tests.test_sumcheck_device import MODULUS, make_inputs, to_bytes, to_int
+from tests.test_sumcheck_device import MODULUS, folded_evaluations, make_inputs, to_bytes, to_int
 
 TAIL_ROWS = 256     # kTailRows of proof/sumcheck_transcript.hip
 FIXED_DEGREE = 5    # kFixedDegree of proof/sumcheck_rows.h
@@ -407,3 +407,86 @@ def test_device_form_back_to_back(gpu_backend, oracle, field_id):
     third = proofs[2].results()
     for h, d in zip(host, third):
         assert np.array_equal(h, d)
+
+
+# n = 2 with one MLE and one product: round degree 1 is k_sumcheck_tail alone, 6 (above kFixedDegree)
+# k_sumcheck_challenge and k_sumcheck_fold_slot
+SWEEP_PRODUCTS = {1: [[0]], 6: [[0] * 6]}
+
+
+def sweep_fields(pos):
+    """the field alternates with the position's parity; every 8th position takes both"""
+    return (pos % 2, 1 - pos % 2) if pos % 8 == 0 else (pos % 2,)
+
+
+def sweep_model(t0, field_id, degree, polynomial=None):
+    t = merlin_ref.TracedTranscript(raw=t0)
+    merlin_ref.sumcheck_begin(t, 1, degree)
+    r = merlin_ref.sumcheck_round(t, field_id, bytes(32 * (degree + 1)) if polynomial is None else polynomial)
+    return t, r
+
+
+@pytest.mark.parametrize("degree", sorted(SWEEP_PRODUCTS))
+def test_sponge_sweep_reaches_every_boundary_class(degree):
+    """a one-round proof from each of the 166 positions crosses the rate boundary in every way a
+    32-byte challenge can (which edges are reached depends on lengths alone)"""
+    reached, positions = set(), {0: 0, 1: 0}
+    for pos, t0 in enumerate(merlin_ref.padded_starts()):
+        for field_id in sweep_fields(pos):
+            reached |= sweep_model(t0, field_id, degree)[0].classes
+            positions[field_id] += 1
+    assert reached == merlin_ref.BOUNDARY_CLASSES, sorted(merlin_ref.BOUNDARY_CLASSES - reached)
+    assert positions == {0: 83, 1: 83 + 21}
+
+
+def test_host_transcript_at_every_sponge_position(cpu_backend):
+    """the host twin of the sweep: strobe128_over / transcript_over are one text for both sponges;
+    bzamd_sumcheck_transcript_begin and _round from each position, every polynomial length"""
+    rng = np.random.default_rng(1900)
+    native = cpu_backend.load().bzamd_sumcheck_transcript_round
+    reached = set()
+    for pos, t0 in enumerate(merlin_ref.padded_starts()):
+        for field_id, degree in ((pos % 2, 1 + pos % 8), (1 - pos % 2, 1 + (pos // 8) % 8)):
+            polynomial = rng.integers(0, 256, 32 * (degree + 1), dtype=np.uint8)
+            model, want = sweep_model(t0, field_id, degree, polynomial.tobytes())
+            t, r = t0.copy(), np.zeros(32, np.uint8)
+            cpu_backend.sumcheck_transcript_begin(t, 1, degree)
+            context = api.bzamd_sumcheck_transcript_context(t.ctypes.data, field_id)
+            native(r.ctypes.data_as(ctypes.c_void_p), ctypes.byref(context),
+                   polynomial.ctypes.data_as(ctypes.c_void_p), degree + 1)
+            assert np.array_equal(t, model.array()), (pos, field_id, degree)
+            assert r.tobytes() == want, (pos, field_id, degree)
+            reached |= model.classes
+    assert reached == merlin_ref.BOUNDARY_CLASSES
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("degree", sorted(SWEEP_PRODUCTS))
+def test_device_form_at_every_sponge_position(gpu_backend, oracle, degree):
+    """a caller who continues a transcript hands the prover any position of the sponge"""
+    import torch
+    dev = torch.device("cuda", 0)
+    n, num_mles, products = 2, 1, SWEEP_PRODUCTS[degree]
+    inputs = [make_inputs(field_id, n, num_mles, products, 1800 + degree + field_id) for field_id in (0, 1)]
+    d_mles = [torch.from_numpy(inp[0].copy()).to(dev) for inp in inputs]
+    side = torch.cuda.Stream(device=dev)
+    reached = set()
+    for pos, t0 in enumerate(merlin_ref.padded_starts()):
+        for field_id in sweep_fields(pos):
+            mles, _, table, terms, _ = inputs[field_id]
+            proof = DeviceProof(field_id, d_mles[field_id], num_mles, table, terms, n, degree, t0)
+            proof.enqueue(gpu_backend, side)
+            side.synchronize()
+            polys, point, evaluations, t = proof.results()
+            where = f"position {pos}, field {field_id}"
+            # the Python model fed the device's own polynomial first: a difference there is the sponge's
+            model, r = sweep_model(t0, field_id, degree, polys[0].tobytes())
+            assert np.array_equal(t, model.array()), f"{where}: the transcript differs from the model"
+            assert point[0].tobytes() == r, f"{where}: the challenge differs from the model"
+            reached |= model.classes
+            want = reference_proof(oracle, field_id, mles, table, terms, n, degree, t0)
+            assert np.array_equal(polys, want[0]), f"{where}: round polynomials differ"
+            assert np.array_equal(point, want[1]), f"{where}: evaluation points differ"
+            assert np.array_equal(t, want[2]), f"{where}: transcripts differ"
+            assert np.array_equal(evaluations, folded_evaluations(field_id, mles, point)), where
+    assert reached == merlin_ref.BOUNDARY_CLASSES
