@@ -162,6 +162,12 @@ def load():
         lib.bzamd_prove_inner_product_device.argtypes = [vp, vp, vp, vp, u64, u64, vp, vp, vp, vp,
                                                          u64, vp]
         lib.bzamd_prove_inner_product_device.restype = None
+    if hasattr(lib, "bzamd_verify_inner_product_device"):
+        lib.bzamd_inner_product_verify_workspace_bytes.argtypes = [u64]
+        lib.bzamd_inner_product_verify_workspace_bytes.restype = u64
+        lib.bzamd_verify_inner_product_device.argtypes = [vp, vp, u64, u64, vp, vp, vp, vp, vp, vp,
+                                                          vp, vp, u64, vp]
+        lib.bzamd_verify_inner_product_device.restype = None
     lib.bzamd_transcript_init.argtypes = [vp, ctypes.c_char_p, u64]
     lib.bzamd_transcript_init.restype = None
     lib.bzamd_num_devices.restype = ctypes.c_int
@@ -363,6 +369,27 @@ def prove_inner_product_device(n, generators_offset, a_device_ptr, b_device_ptr,
                                             transcript_device_ptr, n, generators_offset,
                                             generators_device_ptr, a_device_ptr, b_device_ptr,
                                             workspace_device_ptr, workspace_bytes, stream)
+
+
+def inner_product_verify_workspace_bytes(n):
+    """bytes of device workspace bzamd_verify_inner_product_device needs for n elements (0 for
+    n = 0 or n > 2^30); needs no backend"""
+    return load().bzamd_inner_product_verify_workspace_bytes(n)
+
+
+def verify_inner_product_device(n, generators_offset, b_device_ptr, product_device_ptr,
+                                a_commit_device_ptr, l_device_ptr, r_device_ptr, ap_device_ptr,
+                                transcript_device_ptr, verdict_device_ptr, workspace_device_ptr,
+                                workspace_bytes, generators_device_ptr=None, stream=None):
+    """bzamd_verify_inner_product_device: every operand is a raw device pointer (e.g.
+    tensor.data_ptr()) on the current device; the verdict is one uint32 there (1 accepted, 0
+    rejected); `generators_device_ptr` None: the built-in generators from `generators_offset`.
+    Only enqueues on `stream`."""
+    load().bzamd_verify_inner_product_device(verdict_device_ptr, transcript_device_ptr, n,
+                                             generators_offset, generators_device_ptr,
+                                             b_device_ptr, product_device_ptr, a_commit_device_ptr,
+                                             l_device_ptr, r_device_ptr, ap_device_ptr,
+                                             workspace_device_ptr, workspace_bytes, stream)
 
 
 def verify_inner_product(transcript, n, generators_offset, b_vector, product, a_commit, l_vector,

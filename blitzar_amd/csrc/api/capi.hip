@@ -1614,6 +1614,37 @@ int sxt_curve25519_verify_inner_product(struct sxt_transcript* transcript, uint6
              : 0;
 }
 
+uint64_t bzamd_inner_product_verify_workspace_bytes(uint64_t n) {
+  return proof::inner_product_verify_workspace_bytes(n);
+}
+
+void bzamd_verify_inner_product_device(void* verdict, void* transcript, uint64_t n,
+                                       uint64_t generators_offset, const void* generators,
+                                       const void* b_vector, const void* product,
+                                       const void* a_commit, const void* l_vector,
+                                       const void* r_vector, const void* ap_value,
+                                       void* workspace, uint64_t workspace_bytes, void* stream) {
+  BZ_RELEASE_ASSERT(verdict != nullptr, "verdict must not be null");
+  BZ_RELEASE_ASSERT(transcript != nullptr, "transcript must not be null");
+  BZ_RELEASE_ASSERT(ap_value != nullptr, "ap_value must not be null");
+  BZ_RELEASE_ASSERT(product != nullptr, "product must not be null");
+  BZ_RELEASE_ASSERT(a_commit != nullptr, "a_commit must not be null");
+  BZ_RELEASE_ASSERT(b_vector != nullptr, "b_vector must not be null");
+  BZ_RELEASE_ASSERT(n > 0, "b_vector length must be greater than zero");
+  BZ_RELEASE_ASSERT(n == 1 || (l_vector != nullptr && r_vector != nullptr),
+                    "l_vector and r_vector must not be null when n is bigger than one");
+  BZ_RELEASE_ASSERT(n <= (uint64_t{1} << 30), "inner products are limited to 2^30 elements");
+  // the current device, the caller's stream and workspace, no lease: as the prover's device form
+  api_state& st = state();
+  BZ_RELEASE_ASSERT(st.backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
+  proof::verify_inner_product_device(
+      *st.context_for_current_device(), verdict, transcript, n, generators_offset, generators,
+      static_cast<const u8*>(b_vector), static_cast<const u8*>(product), a_commit,
+      static_cast<const u8*>(l_vector), static_cast<const u8*>(r_vector),
+      static_cast<const u8*>(ap_value), workspace, workspace_bytes,
+      static_cast<hipStream_t>(stream));
+}
+
 namespace {
 // sxt_prove_sumcheck and bzamd_prove_sumcheck* (`name`: the entry point, for the messages);
 // `device_form`: descriptor->mles is memory of the current device, the kernels go on `stream`

@@ -324,5 +324,49 @@ BZ_HD void encode(u8 out[32], const ed29_point& p) {
   for (int i = 0; i < 4; ++i)
     for (int j = 0; j < 8; ++j) out[8 * i + j] = static_cast<u8>(w[i] >> (8 * j));
 }
+
+// Decoding on the 29-bit field: the algorithm and the rejection rule of ristretto::decode in
+// curve/ed25519.h (reference sxt/ristretto/base/byte_conversion.cc:134-190) -- false for a
+// non-canonical s (s >= p), a negative s, a non-square, a negative t and y = 0.  The point comes
+// out in the ABI layout with Z = 1; it is whatever the arithmetic gave when the result is false.
+// The bytes need no alignment.
+BZ_HD bool decode(ed_point& p, const u8 s[32]) {
+  u32 w[8];
+  for (int i = 0; i < 8; ++i) {
+    w[i] = static_cast<u32>(s[4 * i]) | (static_cast<u32>(s[4 * i + 1]) << 8) |
+           (static_cast<u32>(s[4 * i + 2]) << 16) | (static_cast<u32>(s[4 * i + 3]) << 24);
+  }
+  // s < p = 2^255 - 19 as a 256-bit integer, and even
+  bool all_ones = w[7] == 0x7fffffffu;
+  for (int i = 1; i < 7; ++i) all_ones = all_ones && w[i] == 0xffffffffu;
+  const bool below_p = w[7] < 0x7fffffffu || (all_ones && w[0] < 0xffffffedu) ||
+                       (w[7] == 0x7fffffffu && !all_ones);
+  const bool canonical = below_p && (w[0] & 1) == 0;
+  w[7] &= 0x7fffffffu;
+  const fe29 s_ = ed29::unpack_words(w);                                  // B 1
+  const fe29 one = f29::one();
+  const fe29 ss = f29::sq(s_);
+  const fe29 u1 = f29::weak_reduce(f29::sub(one, ss));                    // B 3 -> 1
+  const fe29 u1u1 = f29::sq(u1);
+  const fe29 u2 = f29::add(one, ss);                                      // B 1 (+ 1 in limb 0)
+  const fe29 u2u2 = f29::sq(u2);
+  // -(d u1^2) - u2^2
+  const fe29 d_u1u1 = f29::mul(f29::from_fe51(f51::const_d()), u1u1);
+  const fe29 v = f29::weak_reduce(f29::sub(f29::neg(d_u1u1), u2u2));      // B 4 -> 1
+  const fe29 v_u2u2 = f29::mul(v, u2u2);
+  fe29 inv_sqrt;
+  const bool was_square = sqrt_ratio_m1(inv_sqrt, one, v_u2u2);           // B <= 2
+  fe29 x = f29::mul(inv_sqrt, u2);                                        // 2 * 1
+  fe29 y = f29::mul(f29::mul(inv_sqrt, x), v);                            // 2 * 1, 1 * 1
+  x = f29::mul(x, s_);
+  x = f29::abs(f29::weak_reduce(f29::add(x, x)));                         // B 2 -> 1 -> <= 2
+  y = f29::mul(u1, y);
+  const fe29 t = f29::mul(x, y);                                          // 2 * 1
+  p.X = f29::to_fe51(x);
+  p.Y = f29::to_fe51(y);
+  p.Z = f51::one();
+  p.T = f29::to_fe51(t);
+  return canonical && was_square && !f29::is_negative(t) && !f29::is_zero(y);
+}
 } // namespace ristretto29
 } // namespace bz

@@ -29,6 +29,16 @@ void prove_inner_product_device(msm_context& ctx, u8* l_vector, u8* r_vector, u8
                                 const void* generators, const u8* a_vector, const u8* b_vector,
                                 void* workspace, u64 workspace_bytes, hipStream_t stream);
 
+// The verifier's device form (include/blitzar_amd.h: bzamd_verify_inner_product_device): `verdict`
+// one u32 (1 accepted, 0 rejected), `product` / `ap_value` 32 bytes, `a_commit` one element in ABI
+// layout, the proof where the prover's device form leaves it; everything else as above.
+u64 inner_product_verify_workspace_bytes(u64 n);
+void verify_inner_product_device(msm_context& ctx, void* verdict, void* transcript, u64 n,
+                                 u64 generators_offset, const void* generators, const u8* b_vector,
+                                 const u8* product, const void* a_commit, const u8* l_vector,
+                                 const u8* r_vector, const u8* ap_value, void* workspace,
+                                 u64 workspace_bytes, hipStream_t stream);
+
 // services of api/capi.hip the prover needs
 // generators [offset, offset + n) as raw extended coordinates on the host (cache + derivation)
 void host_builtin_generators_unlocked(api_state& st, ed_point* out, u64 n, u64 offset);

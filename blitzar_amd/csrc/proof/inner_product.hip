@@ -161,12 +161,13 @@ __global__ void __launch_bounds__(256)
 }
 
 // One workgroup: c_l and c_r (canonical) from the `blocks` partials of each, which lie
-// kPartialBlocks apart, into their rows of the scalar columns
+// kPartialBlocks apart, into their rows of the scalar columns (c_r == nullptr: c_l alone)
 __global__ void __launch_bounds__(kPartialBlocks)
     k_cross_finish(u64* __restrict__ c_l, u64* __restrict__ c_r,
                    const s25::fe* __restrict__ partials, u32 blocks) {
   __shared__ s25::fe tree[kPartialBlocks];
-  for (u32 side = 0; side < 2; ++side) {
+  const u32 sides = c_r != nullptr ? 2 : 1;
+  for (u32 side = 0; side < sides; ++side) {
     tree[threadIdx.x] =
         threadIdx.x < blocks ? partials[side * kPartialBlocks + threadIdx.x] : s25::F::zero();
     __syncthreads();
@@ -530,6 +531,258 @@ void prove_inner_product_device(msm_context& ctx, u8* l_vector, u8* r_vector, u8
   enqueue_chain(ctx, l_vector, r_vector, ap_value, static_cast<u8*>(transcript), n,
                 generators_offset, static_cast<const ed_point*>(generators), a_vector, b_vector,
                 workspace, workspace_bytes, stream);
+}
+
+//--------------------------------------------------------------------------------------------------
+// the verifier's chain: everything in the caller's workspace as
+//   generators  G = [a_commit | Q | g_0 .. g_{np-1} | L_0 .. | R_0 ..]
+//   scalars     S = [1 | product | e_Q | e_0 .. e_{np-1} | -x_i^2 .. | -x_i^-2 ..]
+// so that ONE call of the MSM engine with two columns yields
+//   rows S[2 ..] over G[1 ..]  = the commitment the proof's scalars stand for,
+//   rows S[0 .. 2] over G[0 ..] = a_commit + product Q,
+// and the proof is accepted when the two encodings are equal and every L and R decoded.
+//--------------------------------------------------------------------------------------------------
+namespace {
+constexpr u32 kMaxRounds = 30; // n <= 2^30
+
+// what the challenge kernel leaves for the expansion, and the decode kernel for the verdict
+struct verify_slot {
+  s25::fe seed;             // ap prod x_i^-1, plain
+  s25::fe x_sq[kMaxRounds]; // Montgomery form
+  u32 undecodable[2 * kMaxRounds];
+};
+
+constexpr u64 kVerifyRowProduct = 1, kVerifyRowQ = 2, kVerifyRowG = 3;
+
+// One wavefront: the whole transcript of the proof (init, a challenge per round, stored back), then
+// lane i < rounds turns x_i into the rows -x_i^2 and -x_i^-2 and x_sq[i]; lane 0 multiplies the
+// inverses up into the seed.  Column B's rows [1, product] and a_commit's place in G are filled
+// here as well.  rounds = 0 (n = 1): the exponents are b_0 ap on Q and ap on g_0.
+__global__ void __launch_bounds__(64)
+    k_verify_challenges(u8* __restrict__ s, verify_slot* __restrict__ slot,
+                        ed_point* __restrict__ g, u8* transcript, const u8* __restrict__ l_vector,
+                        const u8* __restrict__ r_vector, const u8* __restrict__ ap_value,
+                        const u8* __restrict__ product, const u8* __restrict__ b_vector,
+                        const ed_point* __restrict__ a_commit, u64 n, u32 rounds) {
+  __shared__ wave_state w;
+  __shared__ s25::fe inverses[kMaxRounds];
+  const u32 lane = threadIdx.x;
+  wave_load_transcript(w.t, transcript);
+  init_transcript<wave_sponge>(&w.t, n);
+  s25::fe mine = s25::F::zero();
+  for (u32 i = 0; i < rounds; ++i) {
+    if (lane < 32) {
+      w.l[lane] = l_vector[32 * i + lane];
+      w.r[lane] = r_vector[32 * i + lane];
+    }
+    wave_sponge::sync();
+    const s25::fe x = round_challenge<wave_sponge>(w.x, &w.t, w.l, w.r);
+    if (lane == i) mine = x;
+  }
+  wave_store_transcript(transcript, w.t);
+
+  if (lane < 32) {
+    s[lane] = lane == 0 ? 1 : 0;
+    s[32 * kVerifyRowProduct + lane] = product[lane];
+  }
+  if (lane == 0) g[0] = *a_commit;
+  const s25::fe ap = s25::load(ap_value);
+  const u64 np = u64{1} << rounds;
+  if (rounds == 0) {
+    if (lane == 0) {
+      s25::store(s + 32 * kVerifyRowQ, s25::F::mul(s25::to_mont(s25::load(b_vector)), ap));
+      s25::store(s + 32 * kVerifyRowG, s25::from_mont(s25::to_mont(ap)));
+    }
+    return;
+  }
+  if (lane < rounds) {
+    const s25::fe x_inv = s25::F::invert(mine); // zero for zero, as scalar::inverse
+    const s25::fe x_sq = s25::F::mul(mine, mine);
+    s25::store(s + 32 * (kVerifyRowG + np + lane), s25::from_mont(s25::neg(x_sq)));
+    s25::store(s + 32 * (kVerifyRowG + np + rounds + lane),
+               s25::from_mont(s25::neg(s25::F::mul(x_inv, x_inv))));
+    slot->x_sq[lane] = x_sq;
+    inverses[lane] = x_inv;
+  }
+  wave_sponge::sync();
+  if (lane == 0) {
+    s25::fe all = inverses[0];
+    for (u32 i = 1; i < rounds; ++i) all = s25::F::mul(all, inverses[i]);
+    slot->seed = s25::F::mul(all, ap); // Montgomery form times plain: plain
+  }
+}
+
+// One lane per L / R point: G[first + i] = the decoded point, or the identity and a raised flag
+// for an encoding ristretto::decode rejects -- the chain runs on whatever the proof holds
+__global__ void __launch_bounds__(64)
+    k_verify_decode(ed_point* __restrict__ g, verify_slot* __restrict__ slot,
+                    const u8* __restrict__ l_vector, const u8* __restrict__ r_vector, u32 rounds) {
+  const u32 i = threadIdx.x;
+  if (i >= 2 * rounds) return;
+  const u8* bytes = i < rounds ? l_vector + 32 * i : r_vector + 32 * (i - rounds);
+  ed_point p;
+  const bool ok = ristretto29::decode(p, bytes);
+  g[i] = ok ? p : ed::identity();
+  slot->undecodable[i] = ok ? 0 : 1;
+}
+
+// the caller's np + 1 generators, the last one Q, into [Q | g_0 .. g_{np-1}]
+__global__ void __launch_bounds__(256)
+    k_verify_generators(ed_point* __restrict__ g, const ed_point* __restrict__ generators, u32 np) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > np) return;
+  g[i == np ? 0 : i + 1] = generators[i];
+}
+
+// b into the workspace where the caller's pointer is not 8-byte aligned (as k_load reads it)
+__global__ void __launch_bounds__(256)
+    k_verify_copy_b(u64* __restrict__ out, const u8* __restrict__ b, u32 n) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  for (int k = 0; k < 4; ++k) {
+    const u64 at = 32 * static_cast<u64>(i) + 8 * k;
+    u64 v = 0;
+    for (int j = 7; j >= 0; --j) v = (v << 8) | b[at + j];
+    out[4 * static_cast<u64>(i) + k] = v;
+  }
+}
+
+// e_i = seed prod_{j : bit j of i set} x_sq[rounds - 1 - j], i < np: the closed form of the
+// reference's doubling loop (verification_computation.cc:77-91); canonical rows
+__global__ void __launch_bounds__(256)
+    k_verify_expand(u64* __restrict__ e, const verify_slot* __restrict__ slot, u32 rounds, u32 np) {
+  __shared__ s25::fe x_sq[kMaxRounds];
+  if (threadIdx.x < rounds) x_sq[threadIdx.x] = slot->x_sq[threadIdx.x];
+  __syncthreads();
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= np) return;
+  s25::fe acc = slot->seed;
+  for (u32 j = 0; j < rounds; ++j) {
+    if ((i >> j) & 1) acc = s25::F::mul(x_sq[rounds - 1 - j], acc);
+  }
+  u64 w[4];
+  s25::store_words(w, acc);
+  for (int k = 0; k < 4; ++k) e[4 * static_cast<u64>(i) + k] = w[k];
+}
+
+// One wavefront: accepted when the engine's two encodings are equal and no point failed to decode
+__global__ void __launch_bounds__(64)
+    k_verify_verdict(u32* __restrict__ verdict, const u8* __restrict__ encodings,
+                     const verify_slot* __restrict__ slot, u32 rounds) {
+  const u32 lane = threadIdx.x;
+  bool ok = true;
+  if (lane < 32) ok = encodings[lane] == encodings[32 + lane];
+  if (lane < 2 * rounds) ok = ok && slot->undecodable[lane] == 0;
+  const bool all = __all(ok) != 0;
+  if (lane == 0) *verdict = all ? 1 : 0;
+}
+
+// the caller's workspace of the verifier, for np = 2^rounds
+struct verify_layout {
+  size_t generators, scalars, b, partials, slot, encodings, total;
+  verify_layout(u64 np, u64 rounds) {
+    size_t at = 0;
+    auto take = [&at](size_t bytes) {
+      const size_t here = at;
+      at += device_arena::padded(bytes);
+      return here;
+    };
+    generators = take(sizeof(ed_point) * (2 + np + 2 * rounds));
+    scalars = take(32 * (kVerifyRowG + np + 2 * rounds));
+    b = take(32 * np);
+    partials = take(sizeof(s25::fe) * kPartialBlocks);
+    slot = take(sizeof(verify_slot));
+    encodings = take(64);
+    total = at + 256; // whatever the caller's pointer lacks to a multiple of 256
+  }
+};
+
+void enqueue_verify_chain(msm_context& ctx, u32* verdict, u8* transcript, u64 n,
+                          u64 generators_offset, const ed_point* generators, const u8* b_vector,
+                          const u8* product, const ed_point* a_commit, const u8* l_vector,
+                          const u8* r_vector, const u8* ap_value, void* workspace,
+                          u64 workspace_bytes, hipStream_t stream) {
+  const u64 rounds = ceil_log2(n), np = u64{1} << rounds;
+  const verify_layout layout{np, rounds};
+  BZ_RELEASE_ASSERT(workspace != nullptr && workspace_bytes >= layout.total,
+                    "the inner-product verifier's workspace is too small");
+  const uintptr_t address = reinterpret_cast<uintptr_t>(workspace);
+  u8* base = static_cast<u8*>(workspace) + (256 - address % 256) % 256;
+  ed_point* d_g = reinterpret_cast<ed_point*>(base + layout.generators);
+  u8* d_s = base + layout.scalars;
+  u64* d_e = reinterpret_cast<u64*>(d_s + 32 * kVerifyRowG);
+  u64* d_b = reinterpret_cast<u64*>(base + layout.b);
+  auto* d_partials = reinterpret_cast<s25::fe*>(base + layout.partials);
+  auto* d_slot = reinterpret_cast<verify_slot*>(base + layout.slot);
+  u8* d_encodings = base + layout.encodings;
+  const u32 blocks = static_cast<u32>((np + 255) / 256);
+
+  // G: nothing here depends on the challenges
+  if (generators == nullptr) {
+    builtin_generators_enqueue(d_g + 1, generators_offset + np, 1, stream);
+    builtin_generators_enqueue(d_g + 2, generators_offset, np, stream);
+    g_kernel_launches += 2;
+  } else {
+    hipLaunchKernelGGL(k_verify_generators, dim3(static_cast<u32>((np + 256) / 256)), dim3(256), 0,
+                       stream, d_g + 1, generators, static_cast<u32>(np));
+    g_kernel_launches += 1;
+  }
+  if (rounds != 0) {
+    hipLaunchKernelGGL(k_verify_decode, dim3(1), dim3(64), 0, stream, d_g + 2 + np, d_slot, l_vector,
+                       r_vector, static_cast<u32>(rounds));
+    g_kernel_launches += 1;
+  }
+  hipLaunchKernelGGL(k_verify_challenges, dim3(1), dim3(64), 0, stream, d_s, d_slot, d_g, transcript,
+                     l_vector, r_vector, ap_value, product, b_vector, a_commit, n,
+                     static_cast<u32>(rounds));
+  g_kernel_launches += 1;
+  if (rounds != 0) {
+    hipLaunchKernelGGL(k_verify_expand, dim3(blocks), dim3(256), 0, stream, d_e, d_slot,
+                       static_cast<u32>(rounds), static_cast<u32>(np));
+    // e_Q = <e, b> over the n entries of b
+    const u64* b_words = reinterpret_cast<const u64*>(b_vector);
+    if ((reinterpret_cast<uintptr_t>(b_vector) & 7) != 0) {
+      hipLaunchKernelGGL(k_verify_copy_b, dim3(static_cast<u32>((n + 255) / 256)), dim3(256), 0,
+                         stream, d_b, b_vector, static_cast<u32>(n));
+      g_kernel_launches += 1;
+      b_words = d_b;
+    }
+    const u32 partial_blocks = std::min(kPartialBlocks, static_cast<u32>((n + 255) / 256));
+    hipLaunchKernelGGL(k_inner_product, dim3(partial_blocks), dim3(256), 0, stream, d_partials, d_e,
+                       b_words, static_cast<u32>(n));
+    hipLaunchKernelGGL(k_cross_finish, dim3(1), dim3(kPartialBlocks), 0, stream,
+                       reinterpret_cast<u64*>(d_s + 32 * kVerifyRowQ), static_cast<u64*>(nullptr),
+                       d_partials, partial_blocks);
+    g_kernel_launches += 3;
+  }
+  BZ_HIP_CHECK(hipGetLastError());
+  host_column col_a = byte_column(d_s + 32 * kVerifyRowQ, 1 + np + 2 * rounds, 32, false);
+  col_a.generator_offset = 1;
+  const host_column col_b = byte_column(d_s, 2, 32, false);
+  curve25519_vtable().msm(ctx, d_encodings, 32, false, {col_a, col_b}, nullptr, d_g, stream);
+  hipLaunchKernelGGL(k_verify_verdict, dim3(1), dim3(64), 0, stream, verdict, d_encodings, d_slot,
+                     static_cast<u32>(rounds));
+  BZ_HIP_CHECK(hipGetLastError());
+  g_kernel_launches += 1;
+}
+
+} // namespace
+
+u64 inner_product_verify_workspace_bytes(u64 n) {
+  if (n == 0 || n > (u64{1} << 30)) return 0;
+  const u64 rounds = ceil_log2(n);
+  return verify_layout{u64{1} << rounds, rounds}.total;
+}
+
+void verify_inner_product_device(msm_context& ctx, void* verdict, void* transcript, u64 n,
+                                 u64 generators_offset, const void* generators, const u8* b_vector,
+                                 const u8* product, const void* a_commit, const u8* l_vector,
+                                 const u8* r_vector, const u8* ap_value, void* workspace,
+                                 u64 workspace_bytes, hipStream_t stream) {
+  enqueue_verify_chain(ctx, static_cast<u32*>(verdict), static_cast<u8*>(transcript), n,
+                       generators_offset, static_cast<const ed_point*>(generators), b_vector,
+                       product, static_cast<const ed_point*>(a_commit), l_vector, r_vector, ap_value,
+                       workspace, workspace_bytes, stream);
 }
 
 bool verify_inner_product(api_state& st, void* transcript_bytes, u64 n, u64 generators_offset,

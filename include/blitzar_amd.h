@@ -410,6 +410,30 @@ void bzamd_prove_inner_product_device(void* l_vector, void* r_vector, void* ap_v
                                       const void* b_vector, void* workspace,
                                       uint64_t workspace_bytes, void* stream);
 
+/* The inner-product verifier on a device-resident proof: sxt_curve25519_verify_inner_product as
+ * one chain of kernels.  DEVICE pointers on the current HIP device: verdict (one uint32_t, written
+ * 1 for an accepted proof and 0 for a rejected one), transcript (203 bytes, in / out, used in
+ * place), b_vector (n x 32 bytes, no alignment needed), product, ap_value (32 bytes each),
+ * a_commit (one sxt_ristretto255, any Z), l_vector, r_vector (ceil_log2(n) x 32 bytes each, where
+ * bzamd_prove_inner_product_device left them; may be NULL for n = 1), generators (as for the
+ * prover: NULL for the built-in ones, or np + 1 resident elements, the last one Q) and workspace
+ * (at least bzamd_inner_product_verify_workspace_bytes(n); less aborts).  None of the inputs is
+ * written.  gpu backend only.  The call only enqueues on `stream`: no synchronise, no callback,
+ * no allocation but the MSM engine's own buffers; a later call on the same stream may use the same
+ * workspace.  Same inputs, same verdict and transcript state as
+ * sxt_curve25519_verify_inner_product (unreduced b, product and ap are taken as given; an L or R
+ * that does not decode gives verdict 0 and the whole chain still runs); same limits and aborts.
+ *
+ * bzamd_inner_product_verify_workspace_bytes depends on np alone, needs no backend, and returns 0
+ * for n = 0 and n > 2^30. */
+uint64_t bzamd_inner_product_verify_workspace_bytes(uint64_t n);
+void bzamd_verify_inner_product_device(void* verdict, void* transcript, uint64_t n,
+                                       uint64_t generators_offset, const void* generators,
+                                       const void* b_vector, const void* product,
+                                       const void* a_commit, const void* l_vector,
+                                       const void* r_vector, const void* ap_value,
+                                       void* workspace, uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -22,7 +22,15 @@ device.  All four must return the same proof.  Printed per size, one
 JSON line (appended to --out): medians, min, max, the spread of A (max - min), B1 / A and B2 / A,
 and `b1_not_slower`: B1's median within A's spread of A's median, or better.
 --profile-one N runs a warm-up and one device-form proof of N elements and nothing else: the
-process to put under a kernel trace.  Needs a GPU: there is no CPU fallback."""
+process to put under a kernel trace.  Needs a GPU: there is no CPU fallback.
+
+--verify measures the verifier the same way: A is sxt_curve25519_verify_inner_product of
+--parent-lib, B1 this build's, B2 / B2g bzamd_verify_inner_product_device on a resident proof with
+the built-in / with resident caller generators.  The proof, the commitment and the product are made
+once per size by this build (the B1 child) outside the clock and handed to the other children in a
+file.  Every leg must return 1 and leave the same transcript, and after the timed samples one call
+per leg with a tampered ap must return 0.  --verify --profile-one N: a warm-up and one device-form
+verification."""
 import argparse
 import hashlib
 import json
@@ -30,6 +38,7 @@ import os
 import statistics
 import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -68,6 +77,7 @@ class Worker:
         assert api.init(api.SXT_GPU_BACKEND, 0) == 0
         self.dev = torch.device("cuda", 0)
         self.has_device_form = hasattr(lib, "bzamd_prove_inner_product_device")
+        self.has_verify_form = hasattr(lib, "bzamd_verify_inner_product_device")
 
     def setup(self, n):
         torch, api, dev = self.torch, self.api, self.dev
@@ -122,9 +132,77 @@ class Worker:
         ms = (time.perf_counter() - t_start) * 1e3
         return {"ms": ms, "enqueue_ms": enqueue_ms, "sha256": self.device_hash()}
 
+    def make_statement(self, n, path):
+        """what a verifier is handed, by this build: the proof of inputs(n), the commitment of a and
+        <a, b> mod l"""
+        api = self.api
+        a, b = inputs(n)
+        t0 = api.transcript_new("inner product bench")
+        l, r, ap, _ = api.prove_inner_product(t0, n, 0, a, b)
+        commit = api.msm_projective(0, [(a, False)], api.get_generators(n, 0))[0].view(np.uint64)
+        order = 2**252 + 27742317777372353535851937790883648493
+        words = lambda x: [int.from_bytes(row.tobytes(), "little") for row in x]  # noqa: E731
+        product = sum(x * y for x, y in zip(words(a), words(b))) % order
+        np.savez(path, b=b, t0=t0, l=l, r=r, ap=ap, commit=commit,
+                 product=np.frombuffer(product.to_bytes(32, "little"), np.uint8))
+
+    def setup_verify(self, n, path):
+        torch, api, dev = self.torch, self.api, self.dev
+        self.n = n
+        self.st = {k: v for k, v in np.load(path).items()}
+        self.rounds = max(n - 1, 0).bit_length()
+        tampered = self.st["ap"].copy()
+        tampered[0] ^= 1
+        self.st["ap_tampered"] = tampered
+        if not self.has_verify_form:
+            return
+        np_ = 1 << self.rounds
+        self.d = {k: torch.from_numpy(np.ascontiguousarray(v).view(np.uint8)).to(dev)
+                  for k, v in self.st.items()}
+        self.d_t = torch.zeros_like(self.d["t0"])
+        self.d_verdict = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.workspace_bytes = api.inner_product_verify_workspace_bytes(n)
+        self.d_workspace = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=dev)
+        self.d_generators = torch.empty((np_ + 1, 160), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        api.load().bzamd_ristretto255_generators_device(self.d_generators.data_ptr(), 0, np_ + 1,
+                                                        stream)
+        torch.cuda.synchronize()
+
+    def sample_verify(self, leg, tampered=False):
+        """one timed verification; reading the verdict back and resetting the transcript are
+        outside the clock"""
+        torch, api, st = self.torch, self.api, self.st
+        ap = "ap_tampered" if tampered else "ap"
+        if leg == "blocking":
+            torch.cuda.synchronize()
+            t_start = time.perf_counter()
+            ok, t_after = api.verify_inner_product(st["t0"], self.n, 0, st["b"], st["product"],
+                                                   st["commit"], st["l"], st["r"], st[ap])
+            ms = (time.perf_counter() - t_start) * 1e3
+            return {"ms": ms, "verdict": int(ok), "sha256": proof_hash((t_after,))}
+        d = self.d
+        stream = torch.cuda.current_stream(self.dev)
+        self.d_t.copy_(d["t0"])
+        self.d_verdict.fill_(1 if tampered else 0)
+        torch.cuda.synchronize()
+        t_start = time.perf_counter()
+        api.verify_inner_product_device(
+            self.n, 0, d["b"].data_ptr(), d["product"].data_ptr(), d["commit"].data_ptr(),
+            d["l"].data_ptr(), d["r"].data_ptr(), d[ap].data_ptr(), self.d_t.data_ptr(),
+            self.d_verdict.data_ptr(), self.d_workspace.data_ptr(), self.workspace_bytes,
+            self.d_generators.data_ptr() if leg == "device_generators" else None,
+            stream=stream.cuda_stream)
+        enqueue_ms = (time.perf_counter() - t_start) * 1e3
+        stream.synchronize()
+        ms = (time.perf_counter() - t_start) * 1e3
+        return {"ms": ms, "enqueue_ms": enqueue_ms, "verdict": int(self.d_verdict.cpu().numpy()[0]),
+                "sha256": proof_hash((self.d_t.cpu().numpy(),))}
+
     def serve(self):
         print(json.dumps({"ready": True, "library": self.api.LIB_PATH,
-                          "device_form": self.has_device_form}), flush=True)
+                          "device_form": self.has_device_form,
+                          "verify_form": self.has_verify_form}), flush=True)
         for line in sys.stdin:
             words = line.split()
             if not words or words[0] == "quit":
@@ -132,6 +210,14 @@ class Worker:
             if words[0] == "setup":
                 self.setup(int(words[1]))
                 print(json.dumps({"ok": True}), flush=True)
+            elif words[0] == "statement":
+                self.make_statement(int(words[1]), words[2])
+                print(json.dumps({"ok": True}), flush=True)
+            elif words[0] == "setup_verify":
+                self.setup_verify(int(words[1]), words[2])
+                print(json.dumps({"ok": True}), flush=True)
+            elif words[0] == "verify":
+                print(json.dumps(self.sample_verify(words[1], tampered=len(words) > 2)), flush=True)
             else:
                 print(json.dumps(self.sample(words[1])), flush=True)
 
@@ -177,9 +263,19 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--worker", action="store_true")
     ap.add_argument("--profile-one", type=int)
+    ap.add_argument("--verify", action="store_true")
     args = ap.parse_args()
     if args.worker:
         Worker().serve()
+        return
+    if args.verify and args.profile_one is not None:
+        w = Worker()
+        with tempfile.TemporaryDirectory() as tmp:
+            path = os.path.join(tmp, "statement.npz")
+            w.make_statement(args.profile_one, path)
+            w.setup_verify(args.profile_one, path)
+        w.sample_verify("device_builtin")  # warm: the engine's buffers grow here
+        print(json.dumps({"n": args.profile_one, **w.sample_verify("device_builtin")}), flush=True)
         return
     if args.profile_one is not None:
         w = Worker()
@@ -191,25 +287,41 @@ def main():
     parent, mine, resident = Child(args.parent_lib), Child(None), Child(None)
     children = (parent, mine, resident)
     assert resident.hello["device_form"], "this build has no device form"
+    assert not args.verify or resident.hello["verify_form"], "this build has no device verifier"
+    command = "verify" if args.verify else "sample"
+    tmp = tempfile.TemporaryDirectory()
     legs = [("A_parent_blocking", parent, "blocking"), ("B1_blocking", mine, "blocking"),
             ("B2_device", resident, "device_builtin"),
             ("B2g_device_generators", resident, "device_generators")]
     try:
         for n in (int(x) for x in args.sizes.split(",")):
+            if args.verify:
+                path = os.path.join(tmp.name, f"statement_{n}.npz")
+                mine.ask(f"statement {n} {path}")
             for child in children:
-                child.ask(f"setup {n}")
-            digests = {name: child.ask(f"sample {leg}")["sha256"] for name, child, leg in legs}  # warm
+                child.ask(f"setup_verify {n} {path}" if args.verify else f"setup {n}")
+            warm = {name: child.ask(f"{command} {leg}") for name, child, leg in legs}
+            digests = {name: got["sha256"] for name, got in warm.items()}
             assert len(set(digests.values())) == 1, f"the legs disagree: {digests}"
+            if args.verify:
+                assert all(got["verdict"] == 1 for got in warm.values()), f"not accepted: {warm}"
             ms = {name: [] for name, _, _ in legs}
             enqueue = {name: [] for name, _, _ in legs}
             for _ in range(args.samples):
                 for name, child, leg in legs:
-                    got = child.ask(f"sample {leg}")
+                    got = child.ask(f"{command} {leg}")
+                    assert not args.verify or got["verdict"] == 1, f"{name} rejected the proof"
                     ms[name].append(got["ms"])
                     if "enqueue_ms" in got:
                         enqueue[name].append(got["enqueue_ms"])
             rec = {"n": n, "samples": args.samples, "parent_library": os.path.relpath(parent.hello["library"], ROOT),
                    "library": os.path.relpath(resident.hello["library"], ROOT), "proof_sha256": digests["A_parent_blocking"]}
+            if args.verify:
+                rec["what"] = "verify"
+                tampered = {name: child.ask(f"verify {leg} tampered")["verdict"]
+                            for name, child, leg in legs}
+                assert not any(tampered.values()), f"a tampered ap was accepted: {tampered}"
+                rec["tampered_verdicts"] = tampered
             for name, _, _ in legs:
                 rec[name] = summary(ms[name])
                 if enqueue[name]:
@@ -230,6 +342,7 @@ def main():
     finally:
         for child in children:
             child.close()
+        tmp.cleanup()
 
 
 if __name__ == "__main__":
