@@ -204,6 +204,15 @@ def load():
     lib.bzamd_prove_sumcheck_transcript_device.restype = None
     lib.bzamd_verify_sumcheck.argtypes = [vp, vp, vp, cu, vp, cu, cu]
     lib.bzamd_verify_sumcheck.restype = ctypes.c_int
+    # (an older build selected with BLITZAR_AMD_LIB lacks these three)
+    if hasattr(lib, "bzamd_prove_sumcheck_transcript_device_columns"):
+        lib.bzamd_prove_sumcheck_transcript_columns.argtypes = [vp, vp, vp, vp, cu, vp]
+        lib.bzamd_prove_sumcheck_transcript_columns.restype = None
+        lib.bzamd_sumcheck_transcript_columns_workspace_bytes.argtypes = [cu, vp]
+        lib.bzamd_sumcheck_transcript_columns_workspace_bytes.restype = u64
+        lib.bzamd_prove_sumcheck_transcript_device_columns.argtypes = [vp, vp, vp, vp, cu, vp, vp,
+                                                                       u64, vp]
+        lib.bzamd_prove_sumcheck_transcript_device_columns.restype = None
     _lib = lib
     return lib
 
@@ -600,13 +609,7 @@ def _sumcheck_columns_call(symbol, field_id, descs, num_mles, product_table, pro
     return polys, point, evaluations
 
 
-def prove_sumcheck_columns(field_id, columns, product_table, product_terms, n, round_degree,
-                           callback):
-    """bzamd_prove_sumcheck_columns.  columns: one per MLE, a 1-D numpy integer array (its itemsize
-    is the width, a signed dtype a signed column) or a uint8 [rows, nbytes] array (unsigned
-    integers of nbytes, field elements for nbytes = 32), or an (array, is_signed) pair that says
-    it outright; at most n rows each, the rest is zero
-    -> (polynomials, evaluation_point, mle_evaluations)"""
+def _column_pairs(columns):
     pairs = []
     for c in columns:
         if isinstance(c, tuple):
@@ -614,7 +617,26 @@ def prove_sumcheck_columns(field_id, columns, product_table, product_terms, n, r
         else:
             c = np.ascontiguousarray(c)
             pairs.append((c, c.ndim == 1 and np.issubdtype(c.dtype, np.signedinteger)))
-    descs, keep = make_descriptors(pairs)
+    return pairs
+
+
+def _device_descriptors(descriptors):
+    ds = list(descriptors)
+    descs = (sxt_sequence_descriptor * max(1, len(ds)))()
+    for i, (ptr, rows, nbytes, signed) in enumerate(ds):
+        descs[i] = sxt_sequence_descriptor(nbytes, rows, int(ptr) if rows > 0 else None,
+                                           1 if signed else 0)
+    return descs, len(ds)
+
+
+def prove_sumcheck_columns(field_id, columns, product_table, product_terms, n, round_degree,
+                           callback):
+    """bzamd_prove_sumcheck_columns.  columns: one per MLE, a 1-D numpy integer array (its itemsize
+    is the width, a signed dtype a signed column) or a uint8 [rows, nbytes] array (unsigned
+    integers of nbytes, field elements for nbytes = 32), or an (array, is_signed) pair that says
+    it outright; at most n rows each, the rest is zero
+    -> (polynomials, evaluation_point, mle_evaluations)"""
+    descs, keep = make_descriptors(_column_pairs(columns))
     return _sumcheck_columns_call("bzamd_prove_sumcheck_columns", field_id, descs, len(keep),
                                   product_table, product_terms, n, round_degree, callback)
 
@@ -624,14 +646,68 @@ def prove_sumcheck_device_columns(field_id, descriptors, product_table, product_
     """bzamd_prove_sumcheck_device_columns.  descriptors: one (device_ptr, n_j, nbytes, signed) per
     MLE, memory of the current device; `stream` a hipStream_t as an integer (None: the default
     stream); everything else on the host -> (polynomials, evaluation_point, mle_evaluations)"""
-    ds = list(descriptors)
-    descs = (sxt_sequence_descriptor * max(1, len(ds)))()
-    for i, (ptr, rows, nbytes, signed) in enumerate(ds):
-        descs[i] = sxt_sequence_descriptor(nbytes, rows, int(ptr) if rows > 0 else None,
-                                           1 if signed else 0)
-    return _sumcheck_columns_call("bzamd_prove_sumcheck_device_columns", field_id, descs, len(ds),
+    descs, num_mles = _device_descriptors(descriptors)
+    return _sumcheck_columns_call("bzamd_prove_sumcheck_device_columns", field_id, descs, num_mles,
                                   product_table, product_terms, n, round_degree, callback,
                                   None if stream is None else ctypes.c_void_p(int(stream)))
+
+
+def _transcript_columns(field_id, descs, num_mles, product_table, product_terms, n, round_degree):
+    table = np.ascontiguousarray(product_table, dtype=np.uint8)
+    terms = np.ascontiguousarray(product_terms, dtype=np.uint32)
+    c = bzamd_sumcheck_columns(descs, table.ctypes.data, terms.ctypes.data, n, num_mles,
+                               table.size // SUMCHECK_PRODUCT_STRIDE[field_id], terms.size,
+                               round_degree)
+    return c, (table, terms)
+
+
+def prove_sumcheck_transcript_columns(field_id, columns, product_table, product_terms, n,
+                                      round_degree, transcript, with_evaluations=True):
+    """bzamd_prove_sumcheck_transcript_columns (host operands, either backend).  columns: as
+    prove_sumcheck_columns; transcript: uint8 [203], or None to pass a null pointer
+    -> (polynomials, evaluation_point, mle_evaluations or None, transcript after)"""
+    descs, keep = make_descriptors(_column_pairs(columns))
+    c, _keep = _transcript_columns(field_id, descs, len(keep), product_table, product_terms, n,
+                                   round_degree)
+    num_variables = max((int(n) - 1).bit_length(), 1)
+    polys = np.zeros((num_variables, round_degree + 1, 32), dtype=np.uint8)
+    point = np.zeros((num_variables, 32), dtype=np.uint8)
+    evaluations = np.zeros((len(keep), 32), dtype=np.uint8) if with_evaluations else None
+    t = None if transcript is None else np.ascontiguousarray(transcript, dtype=np.uint8).copy()
+    load().bzamd_prove_sumcheck_transcript_columns(_ptr(polys), _ptr(point), _ptr(evaluations),
+                                                   _ptr(t), field_id, ctypes.byref(c))
+    return polys, point, evaluations, t
+
+
+def sumcheck_transcript_columns_workspace_bytes(field_id, n, num_mles, num_products,
+                                                num_product_terms, round_degree):
+    """bzamd_sumcheck_transcript_columns_workspace_bytes: needs no backend and no descriptors"""
+    c = bzamd_sumcheck_columns(None, None, None, n, num_mles, num_products, num_product_terms,
+                               round_degree)
+    return load().bzamd_sumcheck_transcript_columns_workspace_bytes(field_id, ctypes.byref(c))
+
+
+def prove_sumcheck_transcript_device_columns(field_id, descriptors, product_table, product_terms, n,
+                                             round_degree, polynomials_ptr, evaluation_point_ptr,
+                                             mle_evaluations_ptr, transcript_ptr, workspace_ptr,
+                                             workspace_bytes, stream=None):
+    """bzamd_prove_sumcheck_transcript_device_columns: enqueue only.  descriptors: one (device_ptr,
+    n_j, nbytes, signed) per MLE, or a ready sxt_sequence_descriptor array (the one the MSM took);
+    every *_ptr is memory of the current device as an integer, mle_evaluations_ptr may be None;
+    `stream` a hipStream_t as an integer (None: the default stream).  Results are in the caller's
+    device memory once the stream has run."""
+    if isinstance(descriptors, ctypes.Array):
+        descs, num_mles = descriptors, len(descriptors)
+    else:
+        descs, num_mles = _device_descriptors(descriptors)
+    c, _keep = _transcript_columns(field_id, descs, num_mles, product_table, product_terms, n,
+                                   round_degree)
+    load().bzamd_prove_sumcheck_transcript_device_columns(
+        int(polynomials_ptr), int(evaluation_point_ptr),
+        None if mle_evaluations_ptr is None else int(mle_evaluations_ptr),
+        None if transcript_ptr is None else int(transcript_ptr), field_id, ctypes.byref(c),
+        int(workspace_ptr), workspace_bytes,
+        None if stream is None else ctypes.c_void_p(int(stream)))
 
 
 class MultiexpHandle:

@@ -1707,8 +1707,25 @@ void bzamd_prove_sumcheck_device(void* polynomials, void* evaluation_point, void
 }
 
 namespace {
-// bzamd_prove_sumcheck_columns / _device_columns; the descriptors are checked by the rule of the
-// MSM entry points (check_descriptors), so one array serves both
+// the MLEs of a bzamd_sumcheck_columns, checked by the rule of the MSM entry points
+// (check_descriptors), so one array serves both
+std::vector<proof::sumcheck_column> checked_sumcheck_columns(
+    const struct bzamd_sumcheck_columns* columns) {
+  BZ_RELEASE_ASSERT(columns->num_mles == 0 || columns->mles != nullptr, "descriptors is null");
+  std::vector<proof::sumcheck_column> cols(columns->num_mles);
+  for (u32 j = 0; j < columns->num_mles; ++j) {
+    const sxt_sequence_descriptor& d = columns->mles[j];
+    BZ_RELEASE_ASSERT(d.n == 0 || d.data != nullptr, "descriptor has n > 0 but null data");
+    BZ_RELEASE_ASSERT(d.element_nbytes != 0 && d.element_nbytes <= 32,
+                      "element_nbytes must be in [1, 32]");
+    BZ_RELEASE_ASSERT(!d.is_signed || d.element_nbytes <= 16,
+                      "signed sequences need element_nbytes <= 16");
+    cols[j] = proof::sumcheck_column{d.data, d.n, d.element_nbytes, d.is_signed != 0};
+  }
+  return cols;
+}
+
+// bzamd_prove_sumcheck_columns / _device_columns
 void prove_sumcheck_columns_entry(const char* name, void* polynomials, void* evaluation_point,
                                   void* mle_evaluations, unsigned field_id,
                                   const struct bzamd_sumcheck_columns* columns,
@@ -1721,17 +1738,7 @@ void prove_sumcheck_columns_entry(const char* name, void* polynomials, void* eva
   }
   BZ_RELEASE_ASSERT(columns->product_table != nullptr && columns->product_terms != nullptr,
                     "null table in the sumcheck descriptor");
-  BZ_RELEASE_ASSERT(columns->num_mles == 0 || columns->mles != nullptr, "descriptors is null");
-  std::vector<proof::sumcheck_column> cols(columns->num_mles);
-  for (u32 j = 0; j < columns->num_mles; ++j) {
-    const sxt_sequence_descriptor& d = columns->mles[j];
-    BZ_RELEASE_ASSERT(d.n == 0 || d.data != nullptr, "descriptor has n > 0 but null data");
-    BZ_RELEASE_ASSERT(d.element_nbytes != 0 && d.element_nbytes <= 32,
-                      "element_nbytes must be in [1, 32]");
-    BZ_RELEASE_ASSERT(!d.is_signed || d.element_nbytes <= 16,
-                      "signed sequences need element_nbytes <= 16");
-    cols[j] = proof::sumcheck_column{d.data, d.n, d.element_nbytes, d.is_signed != 0};
-  }
+  const std::vector<proof::sumcheck_column> cols = checked_sumcheck_columns(columns);
   api_state& st = state();
   const proof::sumcheck_inputs in{nullptr,           columns->product_table,
                                   columns->product_terms, columns->n,
@@ -1842,6 +1849,70 @@ void bzamd_prove_sumcheck_transcript_device(void* polynomials, void* evaluation_
   proof::prove_sumcheck_transcript_device(polynomials, evaluation_point, mle_evaluations, transcript,
                                           field_id, in, workspace, workspace_bytes,
                                           static_cast<hipStream_t>(stream));
+}
+
+namespace {
+// the transcript forms over typed columns: arguments and descriptors checked as in
+// prove_sumcheck_columns_entry
+struct transcript_columns_inputs {
+  proof::sumcheck_inputs in;
+  std::vector<proof::sumcheck_column> cols;
+};
+transcript_columns_inputs transcript_columns_form_inputs(
+    const char* name, const void* polynomials, const void* evaluation_point, const void* transcript,
+    const struct bzamd_sumcheck_columns* columns) {
+  if (polynomials == nullptr || evaluation_point == nullptr || columns == nullptr ||
+      transcript == nullptr) {
+    std::fprintf(stderr, "blitzar_amd: null argument to `%s`\n", name);
+    std::abort();
+  }
+  BZ_RELEASE_ASSERT(columns->product_table != nullptr && columns->product_terms != nullptr,
+                    "null table in the sumcheck descriptor");
+  return {proof::sumcheck_inputs{nullptr, columns->product_table, columns->product_terms, columns->n,
+                                 columns->num_mles, columns->num_products,
+                                 columns->num_product_terms, columns->round_degree},
+          checked_sumcheck_columns(columns)};
+}
+} // namespace
+
+void bzamd_prove_sumcheck_transcript_columns(void* polynomials, void* evaluation_point,
+                                             void* mle_evaluations,
+                                             struct sxt_transcript* transcript, unsigned field_id,
+                                             const struct bzamd_sumcheck_columns* columns) {
+  const transcript_columns_inputs c =
+      transcript_columns_form_inputs("bzamd_prove_sumcheck_transcript_columns", polynomials,
+                                     evaluation_point, transcript, columns);
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::prove_sumcheck_transcript_columns(st, polynomials, evaluation_point, mle_evaluations,
+                                           transcript, field_id, c.in, c.cols.data());
+}
+
+uint64_t bzamd_sumcheck_transcript_columns_workspace_bytes(
+    unsigned field_id, const struct bzamd_sumcheck_columns* columns) {
+  BZ_RELEASE_ASSERT(columns != nullptr, "columns must not be null");
+  const proof::sumcheck_inputs in{nullptr, nullptr, nullptr, columns->n, columns->num_mles,
+                                  columns->num_products, columns->num_product_terms,
+                                  columns->round_degree};
+  return proof::sumcheck_transcript_columns_workspace_bytes(field_id, in);
+}
+
+void bzamd_prove_sumcheck_transcript_device_columns(void* polynomials, void* evaluation_point,
+                                                    void* mle_evaluations, void* transcript,
+                                                    unsigned field_id,
+                                                    const struct bzamd_sumcheck_columns* columns,
+                                                    void* workspace, uint64_t workspace_bytes,
+                                                    void* stream) {
+  const transcript_columns_inputs c =
+      transcript_columns_form_inputs("bzamd_prove_sumcheck_transcript_device_columns", polynomials,
+                                     evaluation_point, transcript, columns);
+  // as bzamd_prove_sumcheck_transcript_device: the current device, the caller's stream and
+  // workspace, no lease
+  BZ_RELEASE_ASSERT(state().backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
+  proof::prove_sumcheck_transcript_device_columns(polynomials, evaluation_point, mle_evaluations,
+                                                  transcript, field_id, c.in, c.cols.data(),
+                                                  workspace, workspace_bytes,
+                                                  static_cast<hipStream_t>(stream));
 }
 
 int bzamd_verify_sumcheck(void* expected_sum, void* evaluation_point,

@@ -30,6 +30,21 @@ void prove_sumcheck_transcript_device(void* polynomials, void* evaluation_point,
                                       const sumcheck_inputs& inputs, void* workspace,
                                       u64 workspace_bytes, hipStream_t stream);
 
+// The same three over typed columns (`columns`: inputs.num_mles of them, widths checked by the
+// caller; inputs.mles is not read).  Host form: the columns' data is host memory; GPU backend:
+// uploaded at their own width.  Device form: their data is memory of the current device, read in
+// stream order and never written; the columns array itself is host memory, read before the call
+// returns.  The workspace size depends on the field and the counts of `inputs` alone.
+void prove_sumcheck_transcript_columns(api_state& st, void* polynomials, void* evaluation_point,
+                                       void* mle_evaluations, void* transcript, unsigned field_id,
+                                       const sumcheck_inputs& inputs, const sumcheck_column* columns);
+u64 sumcheck_transcript_columns_workspace_bytes(unsigned field_id, const sumcheck_inputs& inputs);
+void prove_sumcheck_transcript_device_columns(void* polynomials, void* evaluation_point,
+                                              void* mle_evaluations, void* transcript,
+                                              unsigned field_id, const sumcheck_inputs& inputs,
+                                              const sumcheck_column* columns, void* workspace,
+                                              u64 workspace_bytes, hipStream_t stream);
+
 // bzamd_verify_sumcheck (host arithmetic only)
 bool verify_sumcheck(void* expected_sum, void* evaluation_point, void* transcript, unsigned field_id,
                      const void* round_polynomials, unsigned num_variables, unsigned round_degree);

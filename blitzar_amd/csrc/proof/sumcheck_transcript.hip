@@ -24,6 +24,21 @@
 //   round degree 6..8:  c = v,  launches = 1 + 3 v, less the last fold when mle_evaluations is NULL
 // The Merlin logic is proof/transcript.h over wave_sponge: wavefront 0 of the workgroup runs it in
 // lockstep, Keccak-f[1600] with one Keccak lane per SIMD lane.
+//
+// The same chain over typed columns (bzamd_prove_sumcheck_transcript_columns / _device_columns;
+// the columns, their raw residues and the conversion constants c: proof/sumcheck_columns.hip).
+// No engine-form copy of the full tables is made:
+//   n <= 2 kTailRows at round degree <= 5:  k_sumcheck_columns_load writes the n-row engine-form
+//     table (these proofs are tiny), k_sumcheck_tail runs every round;
+//   otherwise round 0 is k_sumcheck_columns_round / _generic on the columns with the multipliers
+//     times their terms' c, k_sumcheck_columns_challenge (k_sumcheck_challenge that also leaves
+//     r c and (1 - r) c for both kinds of column in the slot: four products on one lane, not two
+//     in every lane of the fold), k_sumcheck_columns_fold_slot (raw rows times those factors:
+//     engine form); rounds >= 1 are the chain above on the folded half and quarter.
+// Kernel launches of a proof over columns:
+//   round degree <= 5, n <= 2 kTailRows:  2
+//   round degree <= 5, above:             3 c + 1, c = v - 1 - log2(kTailRows)
+//   round degree 6..8:                    3 v, less the last fold when mle_evaluations is NULL
 #include "blitzar_amd/csrc/proof/sumcheck_transcript.h"
 
 #include <algorithm>
@@ -31,6 +46,7 @@
 #include <mutex>
 #include <vector>
 
+#include "blitzar_amd/csrc/proof/sumcheck_columns.h"
 #include "blitzar_amd/csrc/proof/sumcheck_protocol.h"
 #include "blitzar_amd/csrc/proof/sumcheck_rows.h"
 #include "blitzar_amd/csrc/proof/transcript.h"
@@ -69,8 +85,9 @@ BZ_DEV void store_transcript(u8* transcript, const wave_transcript& w) {
 
 // A round's transcript step, by the 64 lanes of wavefront 0: sum[0 .. length) (LDS) is the round
 // polynomial; stores it and the challenge in the caller's representation, leaves r and 1 - r in
-// engine form in slot[0], slot[1]
-template <class E>
+// engine form in slot[0], slot[1]; with Factors also r c and (1 - r) c in slot[2], slot[3] for the
+// conversion constant c of integer columns and in slot[4], slot[5] for that of 32-byte elements
+template <class E, bool Factors = false>
 BZ_DEV void wave_round(wave_transcript& w, const typename E::F::fe* sum, u32 length, u8* polynomial,
                        u8* point, typename E::F::fe* slot) {
   using F = typename E::F;
@@ -84,17 +101,23 @@ BZ_DEV void wave_round(wave_transcript& w, const typename E::F::fe* sum, u32 len
   if (lane == 0) {
     slot[0] = r;
     slot[1] = fsub<F>(F::one(), r);
+    if constexpr (Factors) {
+      const typename F::fe one_minus_r = fsub<F>(F::one(), r);
+      slot[2] = F::mul(r, E::conversion(false));
+      slot[3] = F::mul(one_minus_r, E::conversion(false));
+      slot[4] = F::mul(r, E::conversion(true));
+      slot[5] = F::mul(one_minus_r, E::conversion(true));
+    }
   }
 }
 
 // One workgroup, in the place of k_sumcheck_finish: adds the workgroups' partials, then the
 // round's transcript step (round 0: the transcript's init first)
-template <class E>
-__global__ void __launch_bounds__(kRoundThreads)
-    k_sumcheck_challenge(u8* __restrict__ polynomials, u8* __restrict__ evaluation_point,
-                         typename E::F::fe* __restrict__ slot, u8* __restrict__ transcript,
-                         const typename E::F::fe* __restrict__ partials, u32 blocks, u32 length,
-                         u32 round, u32 num_variables) {
+template <class E, bool Factors>
+BZ_DEV void challenge_step(u8* __restrict__ polynomials, u8* __restrict__ evaluation_point,
+                           typename E::F::fe* __restrict__ slot, u8* __restrict__ transcript,
+                           const typename E::F::fe* __restrict__ partials, u32 blocks, u32 length,
+                           u32 round, u32 num_variables) {
   using F = typename E::F;
   using fe = typename F::fe;
   __shared__ fe tree[kRoundThreads];
@@ -112,9 +135,29 @@ __global__ void __launch_bounds__(kRoundThreads)
   if (threadIdx.x >= 64) return;
   load_transcript(w, transcript);
   if (round == 0) transcript_begin<wave_sponge>(&w.t, num_variables, length - 1);
-  wave_round<E>(w, sum, length, polynomials + static_cast<size_t>(32) * length * round,
-                evaluation_point + static_cast<size_t>(32) * round, slot);
+  wave_round<E, Factors>(w, sum, length, polynomials + static_cast<size_t>(32) * length * round,
+                         evaluation_point + static_cast<size_t>(32) * round, slot);
   store_transcript(transcript, w);
+}
+template <class E>
+__global__ void __launch_bounds__(kRoundThreads)
+    k_sumcheck_challenge(u8* __restrict__ polynomials, u8* __restrict__ evaluation_point,
+                         typename E::F::fe* __restrict__ slot, u8* __restrict__ transcript,
+                         const typename E::F::fe* __restrict__ partials, u32 blocks, u32 length,
+                         u32 round, u32 num_variables) {
+  challenge_step<E, false>(polynomials, evaluation_point, slot, transcript, partials, blocks, length,
+                           round, num_variables);
+}
+// round 0 over typed columns: the slot takes six elements (wave_round's Factors).  A kernel of its
+// own name rather than a flag on the one above: the two are told apart in a resource report
+template <class E>
+__global__ void __launch_bounds__(kRoundThreads)
+    k_sumcheck_columns_challenge(u8* __restrict__ polynomials, u8* __restrict__ evaluation_point,
+                                 typename E::F::fe* __restrict__ slot, u8* __restrict__ transcript,
+                                 const typename E::F::fe* __restrict__ partials, u32 blocks,
+                                 u32 length, u32 num_variables) {
+  challenge_step<E, true>(polynomials, evaluation_point, slot, transcript, partials, blocks, length, 0,
+                          num_variables);
 }
 
 // k_sumcheck_fold with r and 1 - r from the slot; the last fold (`evaluations`, mid = 1) goes to
@@ -130,6 +173,47 @@ __global__ void __launch_bounds__(256)
   const u64 m = id / mid, i = id % mid;
   typename F::fe v = F::mul(in[m * n + i], slot[1]);
   if (mid + i < n) v = fadd<F>(v, F::mul(slot[0], in[m * n + mid + i]));
+  if (evaluations != nullptr) {
+    E::store(evaluations + E::element_bytes * id, v);
+  } else {
+    out[id] = v;
+  }
+}
+
+// The n-row engine-form table of typed columns, for proofs k_sumcheck_tail runs alone:
+// out[m * n + i] = row i of column m (raw) times its conversion constant, zero past the column's end
+template <class E>
+__global__ void __launch_bounds__(256)
+    k_sumcheck_columns_load(typename E::F::fe* __restrict__ out,
+                            const column_view* __restrict__ views, u64 n, u32 num_mles) {
+  using F = typename E::F;
+  const u64 id = static_cast<u64>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (id >= n * num_mles) return;
+  const u64 m = id / n, i = id % n;
+  const column_view c = views[m];
+  typename F::fe v = F::zero();
+  if (i < c.n) v = F::mul(load_raw<F>(c, i), E::conversion(c.nbytes == E::element_bytes));
+  out[id] = v;
+}
+
+// k_sumcheck_columns_fold (proof/sumcheck_columns.hip) with its factors from the slot as
+// k_sumcheck_columns_challenge leaves it; the last fold (`evaluations`, mid = 1) goes to the caller
+// in the caller's representation
+template <class E>
+__global__ void __launch_bounds__(256)
+    k_sumcheck_columns_fold_slot(typename E::F::fe* __restrict__ out, u8* __restrict__ evaluations,
+                                 const column_view* __restrict__ views, u64 mid, u32 num_mles,
+                                 const typename E::F::fe* __restrict__ slot) {
+  using F = typename E::F;
+  const u64 id = static_cast<u64>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (id >= mid * num_mles) return;
+  const u64 m = id / mid, i = id % mid;
+  const column_view c = views[m];
+  // r c and (1 - r) c of the column's kind
+  const typename F::fe* factors = slot + (c.nbytes == E::element_bytes ? 4 : 2);
+  typename F::fe v = F::zero();
+  if (i < c.n) v = F::mul(load_raw<F>(c, i), factors[1]);
+  if (mid + i < c.n) v = fadd<F>(v, F::mul(factors[0], load_raw<F>(c, mid + i)));
   if (evaluations != nullptr) {
     E::store(evaluations + E::element_bytes * id, v);
   } else {
@@ -249,45 +333,19 @@ host_stage_ring& stage_ring() {
   return *ring;
 }
 
+// Rounds first_round .. v - 1 of the chain on engine-form tables: d_mles holds n rows per MLE (the
+// tables as round first_round reads them), d_next takes the next fold
 template <class E>
-void prove_device(u8* polynomials, u8* evaluation_point, u8* mle_evaluations, u8* transcript,
-                  const sumcheck_inputs& d, void* workspace, u64 workspace_bytes, hipStream_t stream) {
+void chain_rounds(u8* polynomials, u8* evaluation_point, u8* mle_evaluations, u8* transcript,
+                  const sumcheck_inputs& d, u32 first_round, typename E::F::fe* d_mles, u64 n,
+                  typename E::F::fe* d_next, typename E::F::fe* d_partials,
+                  typename E::F::fe* d_slot, const product_desc<typename E::F>* d_products,
+                  const u32* d_terms, hipStream_t stream) {
   using F = typename E::F;
-  using fe = typename F::fe;
   const u32 degree = d.round_degree;
   const u32 length = degree + 1;
   const u32 num_variables = variables_of(d.n);
-  const std::vector<product_desc<F>> products = engine_products<E>(d);
-  const workspace_layout<F> layout{d};
-  BZ_RELEASE_ASSERT(workspace != nullptr && workspace_bytes >= layout.total,
-                    "the sumcheck workspace is too small");
-  const uintptr_t address = reinterpret_cast<uintptr_t>(workspace);
-  u8* base = static_cast<u8*>(workspace) + ((256 - address % 256) % 256) - 256;
-  fe* d_mles = reinterpret_cast<fe*>(base + layout.table);
-  fe* d_next = reinterpret_cast<fe*>(base + layout.folded);
-  fe* d_partials = reinterpret_cast<fe*>(base + layout.partials);
-  fe* d_slot = reinterpret_cast<fe*>(base + layout.slot);
-  auto* d_products = reinterpret_cast<product_desc<F>*>(base + layout.products);
-  u32* d_terms = reinterpret_cast<u32*>(base + layout.terms);
-
-  {
-    const size_t product_bytes = sizeof(product_desc<F>) * products.size();
-    const size_t term_bytes = sizeof(u32) * d.num_product_terms;
-    const std::lock_guard<std::mutex> lock{g_stage_mutex};
-    u8* staged = static_cast<u8*>(stage_ring().acquire(product_bytes + term_bytes));
-    std::memcpy(staged, products.data(), product_bytes);
-    std::memcpy(staged + product_bytes, d.product_terms, term_bytes);
-    BZ_HIP_CHECK(hipMemcpyAsync(d_products, staged, product_bytes, hipMemcpyHostToDevice, stream));
-    BZ_HIP_CHECK(hipMemcpyAsync(d_terms, staged + product_bytes, term_bytes, hipMemcpyHostToDevice,
-                                stream));
-    stage_ring().release(stream);
-  }
-
-  u64 n = d.n;
-  launch_sumcheck_load<E>(stream, d_mles, static_cast<const u8*>(d.mles), n * d.num_mles);
-  BZ_HIP_CHECK(hipGetLastError());
-  g_kernel_launches += 1;
-  for (u32 round = 0; round < num_variables; ++round) {
+  for (u32 round = first_round; round < num_variables; ++round) {
     const u64 mid = u64{1} << (num_variables - 1 - round);
     if (degree <= kFixedDegree && mid <= kTailRows) {
       launch_tail<E, 1>(stream, degree, polynomials, evaluation_point, mle_evaluations, transcript,
@@ -317,6 +375,45 @@ void prove_device(u8* polynomials, u8* evaluation_point, u8* mle_evaluations, u8
     std::swap(d_mles, d_next);
     n = mid;
   }
+}
+
+template <class E>
+void prove_device(u8* polynomials, u8* evaluation_point, u8* mle_evaluations, u8* transcript,
+                  const sumcheck_inputs& d, void* workspace, u64 workspace_bytes, hipStream_t stream) {
+  using F = typename E::F;
+  using fe = typename F::fe;
+  const std::vector<product_desc<F>> products = engine_products<E>(d);
+  const workspace_layout<F> layout{d};
+  BZ_RELEASE_ASSERT(workspace != nullptr && workspace_bytes >= layout.total,
+                    "the sumcheck workspace is too small");
+  const uintptr_t address = reinterpret_cast<uintptr_t>(workspace);
+  u8* base = static_cast<u8*>(workspace) + ((256 - address % 256) % 256) - 256;
+  fe* d_mles = reinterpret_cast<fe*>(base + layout.table);
+  fe* d_next = reinterpret_cast<fe*>(base + layout.folded);
+  fe* d_partials = reinterpret_cast<fe*>(base + layout.partials);
+  fe* d_slot = reinterpret_cast<fe*>(base + layout.slot);
+  auto* d_products = reinterpret_cast<product_desc<F>*>(base + layout.products);
+  u32* d_terms = reinterpret_cast<u32*>(base + layout.terms);
+
+  {
+    const size_t product_bytes = sizeof(product_desc<F>) * products.size();
+    const size_t term_bytes = sizeof(u32) * d.num_product_terms;
+    const std::lock_guard<std::mutex> lock{g_stage_mutex};
+    u8* staged = static_cast<u8*>(stage_ring().acquire(product_bytes + term_bytes));
+    std::memcpy(staged, products.data(), product_bytes);
+    std::memcpy(staged + product_bytes, d.product_terms, term_bytes);
+    BZ_HIP_CHECK(hipMemcpyAsync(d_products, staged, product_bytes, hipMemcpyHostToDevice, stream));
+    BZ_HIP_CHECK(hipMemcpyAsync(d_terms, staged + product_bytes, term_bytes, hipMemcpyHostToDevice,
+                                stream));
+    stage_ring().release(stream);
+  }
+
+  launch_sumcheck_load<E>(stream, d_mles, static_cast<const u8*>(d.mles),
+                          static_cast<u64>(d.n) * d.num_mles);
+  BZ_HIP_CHECK(hipGetLastError());
+  g_kernel_launches += 1;
+  chain_rounds<E>(polynomials, evaluation_point, mle_evaluations, transcript, d, 0, d_mles, d.n,
+                  d_next, d_partials, d_slot, d_products, d_terms, stream);
 }
 
 // the GPU backend's form on host operands: upload, the device chain on the primary stream,
@@ -363,6 +460,185 @@ void prove_uploaded(api_state& st, u8* polynomials, u8* evaluation_point, u8* ml
                               hipMemcpyDeviceToHost, stream));
   BZ_HIP_CHECK(hipStreamSynchronize(stream));
   own.release();
+}
+
+//--------------------------------------------------------------------------------------------------
+// the chain over typed columns
+//--------------------------------------------------------------------------------------------------
+// whether k_sumcheck_tail runs the whole proof (on the table k_sumcheck_columns_load writes)
+bool tail_only(const sumcheck_inputs& d) {
+  return d.round_degree <= kFixedDegree && (u64{1} << (variables_of(d.n) - 1)) <= kTailRows;
+}
+
+// Tail only: the n-row table and the half it folds to.  Otherwise no table at full size: the first
+// fold's half and the quarter, ping-pong.  The views, both product tables (`raw_products`: for
+// round 0, the multipliers times their terms' conversion constants) and the terms are one block,
+// uploaded with one copy.  A function of n, num_mles, num_products, num_product_terms and
+// round_degree alone.
+template <class F> struct columns_workspace_layout {
+  using fe = typename F::fe;
+  size_t table, folded, partials, slot, views, raw_products, products, terms, total;
+  explicit columns_workspace_layout(const sumcheck_inputs& d) {
+    const u64 half = u64{1} << (variables_of(d.n) - 1);
+    const bool tail = tail_only(d);
+    size_t at = 256; // whatever the caller's pointer lacks to a multiple of 256
+    auto take = [&at](size_t bytes) {
+      const size_t here = at;
+      at += device_arena::padded(bytes);
+      return here;
+    };
+    table = take(sizeof(fe) * (tail ? d.n : half) * d.num_mles);
+    folded = take(sizeof(fe) * (tail ? half : (half + 1) / 2) * d.num_mles);
+    partials = take(sizeof(fe) * kRoundBlocks * (kMaxDegree + 1));
+    slot = take(sizeof(fe) * 6);
+    views = take(sizeof(column_view) * d.num_mles);
+    raw_products = take(sizeof(product_desc<F>) * d.num_products);
+    products = take(sizeof(product_desc<F>) * d.num_products);
+    terms = take(sizeof(u32) * d.num_product_terms);
+    total = at;
+  }
+};
+
+// `columns`: d.num_mles of them, data in memory of the current device, lengths checked
+template <class E>
+void prove_device_columns(u8* polynomials, u8* evaluation_point, u8* mle_evaluations, u8* transcript,
+                          const sumcheck_inputs& d, const sumcheck_column* columns, void* workspace,
+                          u64 workspace_bytes, hipStream_t stream) {
+  using F = typename E::F;
+  using fe = typename F::fe;
+  const u32 degree = d.round_degree;
+  const u32 num_variables = variables_of(d.n);
+  const std::vector<product_desc<F>> products = engine_products<E>(d);
+  const columns_workspace_layout<F> layout{d};
+  BZ_RELEASE_ASSERT(workspace != nullptr && workspace_bytes >= layout.total,
+                    "the sumcheck workspace is too small");
+  const uintptr_t address = reinterpret_cast<uintptr_t>(workspace);
+  u8* base = static_cast<u8*>(workspace) + ((256 - address % 256) % 256) - 256;
+  fe* d_table = reinterpret_cast<fe*>(base + layout.table);
+  fe* d_folded = reinterpret_cast<fe*>(base + layout.folded);
+  fe* d_partials = reinterpret_cast<fe*>(base + layout.partials);
+  fe* d_slot = reinterpret_cast<fe*>(base + layout.slot);
+  auto* d_views = reinterpret_cast<column_view*>(base + layout.views);
+  auto* d_raw_products = reinterpret_cast<product_desc<F>*>(base + layout.raw_products);
+  auto* d_products = reinterpret_cast<product_desc<F>*>(base + layout.products);
+  u32* d_terms = reinterpret_cast<u32*>(base + layout.terms);
+
+  {
+    // the block from the views to the terms, laid out in pinned memory as in the workspace
+    const size_t block_bytes = layout.total - layout.views;
+    const std::lock_guard<std::mutex> lock{g_stage_mutex};
+    u8* staged = static_cast<u8*>(stage_ring().acquire(block_bytes));
+    auto* views = reinterpret_cast<column_view*>(staged);
+    for (u32 j = 0; j < d.num_mles; ++j) {
+      const sumcheck_column& c = columns[j];
+      views[j] = column_view{static_cast<const u8*>(c.data), c.n, c.nbytes,
+                             access_of(c.data, c.nbytes), c.is_signed ? 1u : 0u, 0};
+    }
+    auto* raw_products = reinterpret_cast<product_desc<F>*>(staged + (layout.raw_products - layout.views));
+    for (u32 p = 0; p < d.num_products; ++p) {
+      product_desc<F> raw = products[p];
+      for (u32 t = 0; t < raw.num_terms; ++t) {
+        const sumcheck_column& c = columns[d.product_terms[raw.first_term + t]];
+        raw.multiplier = F::mul(raw.multiplier, E::conversion(c.nbytes == E::element_bytes));
+      }
+      raw_products[p] = raw;
+    }
+    std::memcpy(staged + (layout.products - layout.views), products.data(),
+                sizeof(product_desc<F>) * products.size());
+    std::memcpy(staged + (layout.terms - layout.views), d.product_terms,
+                sizeof(u32) * d.num_product_terms);
+    BZ_HIP_CHECK(hipMemcpyAsync(d_views, staged, block_bytes, hipMemcpyHostToDevice, stream));
+    stage_ring().release(stream);
+  }
+
+  if (tail_only(d)) {
+    hipLaunchKernelGGL((k_sumcheck_columns_load<E>),
+                       dim3(ceil_div_u32(static_cast<u64>(d.n) * d.num_mles, 256)), dim3(256), 0,
+                       stream, d_table, d_views, static_cast<u64>(d.n), d.num_mles);
+    BZ_HIP_CHECK(hipGetLastError());
+    g_kernel_launches += 1;
+    chain_rounds<E>(polynomials, evaluation_point, mle_evaluations, transcript, d, 0, d_table, d.n,
+                    d_folded, d_partials, d_slot, d_products, d_terms, stream);
+    return;
+  }
+  const u64 mid = u64{1} << (num_variables - 1);
+  const u32 blocks =
+      static_cast<u32>(std::min<u64>(kRoundBlocks, (mid + kRoundThreads - 1) / kRoundThreads));
+  launch_columns_round<F, 1>(stream, blocks, d_partials, d_views, mid, d_raw_products,
+                             d.num_products, d_terms, degree);
+  BZ_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL((k_sumcheck_columns_challenge<E>), dim3(1), dim3(kRoundThreads), 0, stream,
+                     polynomials, evaluation_point, d_slot, transcript, d_partials, blocks,
+                     degree + 1, num_variables);
+  BZ_HIP_CHECK(hipGetLastError());
+  g_kernel_launches += 2;
+  const bool last = num_variables == 1;
+  if (last && mle_evaluations == nullptr) return;
+  hipLaunchKernelGGL((k_sumcheck_columns_fold_slot<E>), dim3(ceil_div_u32(mid * d.num_mles, 256)),
+                     dim3(256), 0, stream, d_table, last ? mle_evaluations : nullptr, d_views, mid,
+                     d.num_mles, d_slot);
+  BZ_HIP_CHECK(hipGetLastError());
+  g_kernel_launches += 1;
+  chain_rounds<E>(polynomials, evaluation_point, mle_evaluations, transcript, d, 1, d_table, mid,
+                  d_folded, d_partials, d_slot, d_products, d_terms, stream);
+}
+
+// the GPU backend's form on host columns: upload them at their own width, the device chain on the
+// primary stream, download, one synchronise
+template <class E>
+void prove_uploaded_columns(api_state& st, u8* polynomials, u8* evaluation_point,
+                            u8* mle_evaluations, u8* transcript, const sumcheck_inputs& d,
+                            const sumcheck_column* columns) {
+  using F = typename E::F;
+  const int device = st.primary().device;
+  hipStream_t stream = st.primary().stream;
+  BZ_HIP_CHECK(hipSetDevice(device));
+  const u32 num_variables = variables_of(d.n);
+  const size_t poly_bytes = static_cast<size_t>(32) * (d.round_degree + 1) * num_variables;
+  const size_t point_bytes = static_cast<size_t>(32) * num_variables;
+  const size_t evaluation_bytes = static_cast<size_t>(32) * d.num_mles;
+  const columns_workspace_layout<F> layout{d};
+  size_t arena_bytes = device_arena::padded(poly_bytes) + device_arena::padded(point_bytes) +
+                       device_arena::padded(evaluation_bytes) + 256 + layout.total;
+  for (u32 j = 0; j < d.num_mles; ++j) {
+    arena_bytes += device_arena::padded(columns[j].n * columns[j].nbytes);
+  }
+  g_sumcheck_arena_bytes.store(arena_bytes);
+  device_arena own;
+  own.reset(arena_bytes, stream);
+  std::vector<sumcheck_column> on_device(columns, columns + d.num_mles);
+  for (sumcheck_column& c : on_device) {
+    const size_t bytes = c.n * c.nbytes;
+    u8* staged = own.take<u8>(bytes);
+    if (bytes != 0) BZ_HIP_CHECK(hipMemcpyAsync(staged, c.data, bytes, hipMemcpyHostToDevice, stream));
+    c.data = staged;
+  }
+  u8* d_polynomials = own.take<u8>(poly_bytes);
+  u8* d_point = own.take<u8>(point_bytes);
+  u8* d_evaluations = own.take<u8>(evaluation_bytes);
+  u8* d_transcript = own.take<u8>(sizeof(transcript_state));
+  u8* d_workspace = own.take<u8>(layout.total);
+  BZ_HIP_CHECK(hipMemcpyAsync(d_transcript, transcript, sizeof(transcript_state),
+                              hipMemcpyHostToDevice, stream));
+  prove_device_columns<E>(d_polynomials, d_point,
+                          mle_evaluations != nullptr ? d_evaluations : nullptr, d_transcript, d,
+                          on_device.data(), d_workspace, layout.total, stream);
+  BZ_HIP_CHECK(hipMemcpyAsync(polynomials, d_polynomials, poly_bytes, hipMemcpyDeviceToHost, stream));
+  BZ_HIP_CHECK(hipMemcpyAsync(evaluation_point, d_point, point_bytes, hipMemcpyDeviceToHost, stream));
+  if (mle_evaluations != nullptr) {
+    BZ_HIP_CHECK(hipMemcpyAsync(mle_evaluations, d_evaluations, evaluation_bytes,
+                                hipMemcpyDeviceToHost, stream));
+  }
+  BZ_HIP_CHECK(hipMemcpyAsync(transcript, d_transcript, sizeof(transcript_state),
+                              hipMemcpyDeviceToHost, stream));
+  BZ_HIP_CHECK(hipStreamSynchronize(stream));
+  own.release();
+}
+
+void check_column_lengths(const sumcheck_inputs& d, const sumcheck_column* columns) {
+  for (u32 j = 0; j < d.num_mles; ++j) {
+    BZ_RELEASE_ASSERT(columns[j].n <= d.n, "a sumcheck column is longer than n");
+  }
 }
 
 struct round_context {
@@ -470,6 +746,60 @@ void prove_sumcheck_transcript_device(void* polynomials, void* evaluation_point,
     prove_device<grumpkin_elements>(static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
                                     static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript),
                                     d, workspace, workspace_bytes, stream);
+  } else {
+    BZ_RELEASE_ASSERT(false, "unsupported field id");
+  }
+}
+
+void prove_sumcheck_transcript_columns(api_state& st, void* polynomials, void* evaluation_point,
+                                       void* mle_evaluations, void* transcript, unsigned field_id,
+                                       const sumcheck_inputs& d, const sumcheck_column* columns) {
+  check_sumcheck_limits(d);
+  BZ_RELEASE_ASSERT(field_id <= 1, "unsupported field id");
+  if (st.backend != 2) {
+    // the host round loop over the columns with the host Merlin as its callback
+    sumcheck_transcript_begin(transcript, variables_of(d.n), d.round_degree);
+    round_context context{transcript, field_id};
+    prove_sumcheck_columns(st, polynomials, evaluation_point, mle_evaluations, field_id, d, columns,
+                           reinterpret_cast<void*>(&round_callback), &context);
+    return;
+  }
+  check_column_lengths(d, columns);
+  if (field_id == 0) {
+    prove_uploaded_columns<scalar25519_elements>(
+        st, static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
+        static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript), d, columns);
+  } else {
+    prove_uploaded_columns<grumpkin_elements>(
+        st, static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
+        static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript), d, columns);
+  }
+}
+
+u64 sumcheck_transcript_columns_workspace_bytes(unsigned field_id, const sumcheck_inputs& d) {
+  check_sumcheck_limits(d);
+  BZ_RELEASE_ASSERT(field_id <= 1, "unsupported field id");
+  return field_id == 0 ? columns_workspace_layout<scalar25_field>{d}.total
+                       : columns_workspace_layout<grumpkin_fq29>{d}.total;
+}
+
+void prove_sumcheck_transcript_device_columns(void* polynomials, void* evaluation_point,
+                                              void* mle_evaluations, void* transcript,
+                                              unsigned field_id, const sumcheck_inputs& d,
+                                              const sumcheck_column* columns, void* workspace,
+                                              u64 workspace_bytes, hipStream_t stream) {
+  check_sumcheck_limits(d);
+  check_column_lengths(d, columns);
+  if (field_id == 0) {
+    prove_device_columns<scalar25519_elements>(
+        static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
+        static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript), d, columns, workspace,
+        workspace_bytes, stream);
+  } else if (field_id == 1) {
+    prove_device_columns<grumpkin_elements>(
+        static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
+        static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript), d, columns, workspace,
+        workspace_bytes, stream);
   } else {
     BZ_RELEASE_ASSERT(false, "unsupported field id");
   }

@@ -375,6 +375,37 @@ void bzamd_prove_sumcheck_transcript_device(void* polynomials, void* evaluation_
                                             const struct sumcheck_descriptor* descriptor,
                                             void* workspace, uint64_t workspace_bytes, void* stream);
 
+/* Both over typed columns: commit the columns with bzamd_msm_device, then prove over the same
+ * descriptors on the same stream, with no host round trip and no widened copy.  The three entry
+ * points write the bytes, and leave the transcript state, that bzamd_prove_sumcheck_transcript /
+ * _transcript_device produce for the columns widened to 32-byte elements and padded with zero rows
+ * to n.  Descriptors, limits and aborts are those of bzamd_prove_sumcheck_columns; a null
+ * transcript aborts. */
+/* HOST operands (mles[j].data included), blocking, cpu and gpu backends.  The gpu backend uploads
+ * the columns at their own width, runs the device form below and synchronises once, at the end. */
+void bzamd_prove_sumcheck_transcript_columns(void* polynomials, void* evaluation_point,
+                                             void* mle_evaluations,
+                                             struct sxt_transcript* transcript, unsigned field_id,
+                                             const struct bzamd_sumcheck_columns* columns);
+/* DEVICE pointers on the current HIP device: mles[j].data (any address; read in stream order,
+ * never written), polynomials, evaluation_point, mle_evaluations (may be NULL), transcript (203
+ * bytes, in / out) and workspace (bzamd_sumcheck_transcript_columns_workspace_bytes of the same
+ * field and counts, at least; less aborts; any alignment).  HOST: the struct, the descriptors, the
+ * product table and the terms, which are read before the call returns.  gpu backend only.  The
+ * call only enqueues on `stream`: no synchronise, no allocation, no callback.  Round 0 and the
+ * first fold read the columns where they lie: the workspace holds the folded half and quarter (27
+ * bytes per padded row and MLE, against 54 of the 32-byte form), or for n <= 512 at round degree
+ * <= 5 the n-row table.  The workspace size needs no backend and depends on field_id, n, num_mles,
+ * num_products, num_product_terms and round_degree only (mles and the tables may be NULL). */
+uint64_t bzamd_sumcheck_transcript_columns_workspace_bytes(
+    unsigned field_id, const struct bzamd_sumcheck_columns* columns);
+void bzamd_prove_sumcheck_transcript_device_columns(void* polynomials, void* evaluation_point,
+                                                    void* mle_evaluations, void* transcript,
+                                                    unsigned field_id,
+                                                    const struct bzamd_sumcheck_columns* columns,
+                                                    void* workspace, uint64_t workspace_bytes,
+                                                    void* stream);
+
 /* The matching verifier (the reference's prfsk::verify_sumcheck_no_evaluation with that
  * transcript): host arithmetic only, needs no backend.  round_polynomials: num_variables x
  * (round_degree + 1) elements.  Every round checks 2 p[0] + p[1] + .. + p[D] == expected_sum, draws

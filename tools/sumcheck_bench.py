@@ -5,6 +5,8 @@ length `degree`, a hash transcript), for both fields of the ABI.
 
     python tools/sumcheck_bench.py <n> <degree> <num_products> <num_samples> [--fields 0,1]
                                    [--column-bytes 1|2|4|8] [--transcript]
+    python tools/sumcheck_bench.py <n> <degree> <num_products> <num_samples> --transcript
+                                   --column-bytes W
 
 Timed, with a device synchronise inside the clock, after one untimed call:
   host    sxt_prove_sumcheck: the tables start in host memory (their upload is part of the call);
@@ -23,6 +25,14 @@ and two legs on resident tables alternate in one process, A, B, A, B, ..., after
   B  bzamd_prove_sumcheck_transcript_device: enqueue only, timed to a stream synchronise after it.
 Both must leave the same bytes.  Printed per field: the medians, the spread of the A samples (max -
 min) and whether B's median is within that spread of A's or better (`b_not_slower`).
+With --transcript --column-bytes W the MLEs are signed integers of W bytes and the two legs are the
+enqueue-only forms, alternating B, C, B, C, ... in one process after one untimed call each:
+  B  bzamd_prove_sumcheck_transcript_device on the values widened to 32 bytes;
+  C  bzamd_prove_sumcheck_transcript_device_columns on the W-byte columns.
+Both must leave the same outputs and transcript.  Printed per field: the medians, the spread of the
+B samples, whether C's median is within that spread of B's or better (`c_not_slower`), and the
+workspace bytes of both forms.  (Field 1 draws its values from a pool of 2^16 integers, widened in
+Python integers once: the kernels' time does not depend on the values.)
 BLITZAR_AMD_LIB selects the library (A/B against another build in one session); a library without
 bzamd_prove_sumcheck_device reports the device leg as absent.  Prints one JSON line.  Needs a GPU:
 there is no CPU fallback."""
@@ -171,6 +181,82 @@ def transcript_legs(field_id, dev, n, degree, num_products, num_samples):
             "polynomials_sha256": hashlib.sha256(got[0].tobytes()).hexdigest()[:16]}
 
 
+def transcript_columns_legs(field_id, dev, n, degree, num_products, num_samples, width):
+    """--transcript --column-bytes: legs B and C of the docstring for one field"""
+    num_mles = degree * num_products
+    rounds = max((n - 1).bit_length(), 1)
+    rng = np.random.default_rng(1 + field_id)
+    if field_id == 0:
+        values, raw = integer_columns(rng, width, n, num_mles)
+        mles = widen(field_id, values)
+    else:
+        pool_values, pool_raw = integer_columns(rng, width, 1 << 16, 1)
+        pool_wide = widen(field_id, pool_values)
+        pick = rng.integers(0, 1 << 16, (num_mles, n))
+        raw, mles = pool_raw[0][pick], pool_wide[0][pick]
+        del pick
+    table = np.zeros((num_products, api.SUMCHECK_PRODUCT_STRIDE[field_id]), np.uint8)
+    table[:, :32] = random_elements(rng, field_id, num_products)
+    table[:, 32:36] = np.frombuffer(np.uint32(degree).tobytes(), np.uint8)
+    terms = np.arange(num_mles, dtype=np.uint32)
+    d_mles = torch.from_numpy(np.ascontiguousarray(mles)).to(dev)
+    d_raw = torch.from_numpy(np.ascontiguousarray(raw)).to(dev)
+    del mles, raw
+    descriptors = [(d_raw.data_ptr() + j * n * width, n, width, True) for j in range(num_mles)]
+    d_t0 = torch.from_numpy(api.transcript_new("sumcheck bench")).to(dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    sizes = {"b": api.sumcheck_transcript_workspace_bytes(field_id, n, num_mles, num_products,
+                                                          num_mles, degree),
+             "c": api.sumcheck_transcript_columns_workspace_bytes(field_id, n, num_mles,
+                                                                  num_products, num_mles, degree)}
+    buffers = {}
+    for leg in ("b", "c"):
+        buffers[leg] = {
+            "t": torch.zeros_like(d_t0),
+            "polys": torch.zeros((rounds, degree + 1, 32), dtype=torch.uint8, device=dev),
+            "point": torch.zeros((rounds, 32), dtype=torch.uint8, device=dev),
+            "evaluations": torch.zeros((num_mles, 32), dtype=torch.uint8, device=dev),
+            "workspace": torch.empty(sizes[leg], dtype=torch.uint8, device=dev)}
+
+    def leg_b():
+        o = buffers["b"]
+        o["t"].copy_(d_t0)
+        api.prove_sumcheck_transcript_device(
+            field_id, d_mles.data_ptr(), num_mles, table, terms, n, degree, o["polys"].data_ptr(),
+            o["point"].data_ptr(), o["evaluations"].data_ptr(), o["t"].data_ptr(),
+            o["workspace"].data_ptr(), sizes["b"], stream=stream)
+
+    def leg_c():
+        o = buffers["c"]
+        o["t"].copy_(d_t0)
+        api.prove_sumcheck_transcript_device_columns(
+            field_id, descriptors, table, terms, n, degree, o["polys"].data_ptr(),
+            o["point"].data_ptr(), o["evaluations"].data_ptr(), o["t"].data_ptr(),
+            o["workspace"].data_ptr(), sizes["c"], stream=stream)
+
+    for leg in (leg_b, leg_c):
+        leg()  # warm
+        torch.cuda.synchronize()
+    ms = {"b": [], "c": []}
+    for _ in range(num_samples):
+        for name, leg in (("b", leg_b), ("c", leg_c)):
+            t_start = time.perf_counter()
+            leg()
+            torch.cuda.synchronize()
+            ms[name].append((time.perf_counter() - t_start) * 1e3)
+    same = all(torch.equal(buffers["b"][k], buffers["c"][k])
+               for k in ("t", "polys", "point", "evaluations"))
+    assert same, "the columns form disagrees with the device transcript form"
+    b, c = summary(ms["b"]), summary(ms["c"])
+    spread = b["max_ms"] - b["min_ms"]
+    return {"B_device_transcript": b, "C_device_transcript_columns": c,
+            "b_spread_ms": round(spread, 4), "c_over_b": round(c["median_ms"] / b["median_ms"], 4),
+            "c_not_slower": bool(c["median_ms"] <= b["median_ms"] + spread), "c_equals_b": True,
+            "workspace_bytes": {"B": int(sizes["b"]), "C": int(sizes["c"])},
+            "polynomials_sha256":
+                hashlib.sha256(buffers["c"]["polys"].cpu().numpy().tobytes()).hexdigest()[:16]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("n", type=int)
@@ -197,7 +283,15 @@ def main():
         assert hasattr(lib, "bzamd_prove_sumcheck_transcript_device"), \
             "--transcript needs a library with the device transcript form"
         rec["mode"] = "transcript"
+        if args.column_bytes is not None:
+            assert hasattr(lib, "bzamd_prove_sumcheck_transcript_device_columns"), \
+                "--transcript --column-bytes needs a library with the columns transcript form"
+            rec["column_bytes"] = args.column_bytes
         for field_id in (int(x) for x in args.fields.split(",")):
+            if args.column_bytes is not None:
+                rec["fields"][str(field_id)] = transcript_columns_legs(
+                    field_id, dev, n, degree, num_products, args.num_samples, args.column_bytes)
+                continue
             rec["fields"][str(field_id)] = transcript_legs(field_id, dev, n, degree, num_products,
                                                            args.num_samples)
         print(json.dumps(rec), flush=True)
