@@ -1646,31 +1646,51 @@ void bzamd_verify_inner_product_device(void* verdict, void* transcript, uint64_t
 }
 
 namespace {
-// sxt_prove_sumcheck and bzamd_prove_sumcheck* (`name`: the entry point, for the messages);
-// `device_form`: descriptor->mles is memory of the current device, the kernels go on `stream`
-void prove_sumcheck_entry(const char* name, void* polynomials, void* evaluation_point,
-                          void* mle_evaluations, unsigned field_id,
-                          const struct sumcheck_descriptor* descriptor, void* transcript_callback,
-                          void* transcript_context, bool device_form, void* stream) {
-  if (polynomials == nullptr || evaluation_point == nullptr || descriptor == nullptr ||
-      transcript_callback == nullptr) {
+// what the sumcheck entry points share.  `name`: the entry point, for the message
+void check_arguments(const char* name, bool all_present) {
+  if (!all_present) {
     std::fprintf(stderr, "blitzar_amd: null argument to `%s`\n", name);
     std::abort();
   }
+}
+// the prover's inputs; the workspace-size entry points read the counts alone (`tables` false).
+// Overloads: C++ linkage inside this file's extern "C"
+extern "C++" proof::sumcheck_inputs inputs_of(const struct sumcheck_descriptor& d,
+                                              bool tables = true) {
+  return {tables ? d.mles : nullptr, tables ? d.product_table : nullptr,
+          tables ? d.product_terms : nullptr, d.n, d.num_mles, d.num_products,
+          d.num_product_terms, d.round_degree};
+}
+extern "C++" proof::sumcheck_inputs inputs_of(const struct bzamd_sumcheck_columns& c,
+                                              bool tables = true) {
+  return {nullptr, tables ? c.product_table : nullptr, tables ? c.product_terms : nullptr, c.n,
+          c.num_mles, c.num_products, c.num_product_terms, c.round_degree};
+}
+// The device forms: the current device, the caller's stream, memory of the call's own or the
+// caller's.  None of the backend's per-device state is touched, so no lease is taken (and a
+// transcript callback may call back freely)
+proof::sumcheck_device_tables device_form(void* stream) {
+  BZ_RELEASE_ASSERT(state().backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
+  proof::sumcheck_device_tables tables{0, static_cast<hipStream_t>(stream)};
+  BZ_HIP_CHECK(hipGetDevice(&tables.device));
+  return tables;
+}
+
+// sxt_prove_sumcheck and bzamd_prove_sumcheck*; `device`: descriptor->mles is memory of the current
+// device, the kernels go on `stream`
+void prove_sumcheck_entry(const char* name, void* polynomials, void* evaluation_point,
+                          void* mle_evaluations, unsigned field_id,
+                          const struct sumcheck_descriptor* descriptor, void* transcript_callback,
+                          void* transcript_context, bool device, void* stream) {
+  check_arguments(name, polynomials != nullptr && evaluation_point != nullptr &&
+                            descriptor != nullptr && transcript_callback != nullptr);
   BZ_RELEASE_ASSERT(descriptor->mles != nullptr && descriptor->product_table != nullptr &&
                         descriptor->product_terms != nullptr,
                     "null table in the sumcheck descriptor");
   api_state& st = state();
-  const proof::sumcheck_inputs in{descriptor->mles,         descriptor->product_table,
-                                  descriptor->product_terms, descriptor->n,
-                                  descriptor->num_mles,      descriptor->num_products,
-                                  descriptor->num_product_terms, descriptor->round_degree};
-  if (device_form) {
-    // the current device, the caller's stream, memory of the call's own: none of the backend's
-    // per-device state is touched, so no lease is taken and the callback may call back freely
-    BZ_RELEASE_ASSERT(st.backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
-    proof::sumcheck_device_tables tables{0, static_cast<hipStream_t>(stream)};
-    BZ_HIP_CHECK(hipGetDevice(&tables.device));
+  const proof::sumcheck_inputs in = inputs_of(*descriptor);
+  if (device) {
+    const proof::sumcheck_device_tables tables = device_form(stream);
     proof::prove_sumcheck(st, polynomials, evaluation_point, mle_evaluations, field_id, in,
                           transcript_callback, transcript_context, nullptr, &tables);
     return;
@@ -1730,25 +1750,16 @@ void prove_sumcheck_columns_entry(const char* name, void* polynomials, void* eva
                                   void* mle_evaluations, unsigned field_id,
                                   const struct bzamd_sumcheck_columns* columns,
                                   void* transcript_callback, void* transcript_context,
-                                  bool device_form, void* stream) {
-  if (polynomials == nullptr || evaluation_point == nullptr || columns == nullptr ||
-      transcript_callback == nullptr) {
-    std::fprintf(stderr, "blitzar_amd: null argument to `%s`\n", name);
-    std::abort();
-  }
+                                  bool device, void* stream) {
+  check_arguments(name, polynomials != nullptr && evaluation_point != nullptr &&
+                            columns != nullptr && transcript_callback != nullptr);
   BZ_RELEASE_ASSERT(columns->product_table != nullptr && columns->product_terms != nullptr,
                     "null table in the sumcheck descriptor");
   const std::vector<proof::sumcheck_column> cols = checked_sumcheck_columns(columns);
   api_state& st = state();
-  const proof::sumcheck_inputs in{nullptr,           columns->product_table,
-                                  columns->product_terms, columns->n,
-                                  columns->num_mles, columns->num_products,
-                                  columns->num_product_terms, columns->round_degree};
-  if (device_form) {
-    // as bzamd_prove_sumcheck_device: the current device, the caller's stream, no lease
-    BZ_RELEASE_ASSERT(st.backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
-    proof::sumcheck_device_tables tables{0, static_cast<hipStream_t>(stream)};
-    BZ_HIP_CHECK(hipGetDevice(&tables.device));
+  const proof::sumcheck_inputs in = inputs_of(*columns);
+  if (device) {
+    const proof::sumcheck_device_tables tables = device_form(stream);
     proof::prove_sumcheck_columns(st, polynomials, evaluation_point, mle_evaluations, field_id, in,
                                   cols.data(), transcript_callback, transcript_context, nullptr,
                                   &tables);
@@ -1800,18 +1811,12 @@ namespace {
 proof::sumcheck_inputs transcript_form_inputs(const char* name, const void* polynomials,
                                               const void* evaluation_point, const void* transcript,
                                               const struct sumcheck_descriptor* descriptor) {
-  if (polynomials == nullptr || evaluation_point == nullptr || descriptor == nullptr ||
-      transcript == nullptr) {
-    std::fprintf(stderr, "blitzar_amd: null argument to `%s`\n", name);
-    std::abort();
-  }
+  check_arguments(name, polynomials != nullptr && evaluation_point != nullptr &&
+                            descriptor != nullptr && transcript != nullptr);
   BZ_RELEASE_ASSERT(descriptor->mles != nullptr && descriptor->product_table != nullptr &&
                         descriptor->product_terms != nullptr,
                     "null table in the sumcheck descriptor");
-  return proof::sumcheck_inputs{descriptor->mles,         descriptor->product_table,
-                                descriptor->product_terms, descriptor->n,
-                                descriptor->num_mles,      descriptor->num_products,
-                                descriptor->num_product_terms, descriptor->round_degree};
+  return inputs_of(*descriptor);
 }
 } // namespace
 
@@ -1829,10 +1834,7 @@ void bzamd_prove_sumcheck_transcript(void* polynomials, void* evaluation_point,
 uint64_t bzamd_sumcheck_transcript_workspace_bytes(unsigned field_id,
                                                    const struct sumcheck_descriptor* descriptor) {
   BZ_RELEASE_ASSERT(descriptor != nullptr, "descriptor must not be null");
-  const proof::sumcheck_inputs in{nullptr, nullptr, nullptr, descriptor->n, descriptor->num_mles,
-                                  descriptor->num_products, descriptor->num_product_terms,
-                                  descriptor->round_degree};
-  return proof::sumcheck_transcript_workspace_bytes(field_id, in);
+  return proof::sumcheck_transcript_workspace_bytes(field_id, inputs_of(*descriptor, false));
 }
 
 void bzamd_prove_sumcheck_transcript_device(void* polynomials, void* evaluation_point,
@@ -1843,12 +1845,9 @@ void bzamd_prove_sumcheck_transcript_device(void* polynomials, void* evaluation_
   const proof::sumcheck_inputs in =
       transcript_form_inputs("bzamd_prove_sumcheck_transcript_device", polynomials,
                              evaluation_point, transcript, descriptor);
-  // the current device, the caller's stream and workspace: none of the backend's per-device state
-  // is touched, so no lease is taken
-  BZ_RELEASE_ASSERT(state().backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
   proof::prove_sumcheck_transcript_device(polynomials, evaluation_point, mle_evaluations, transcript,
                                           field_id, in, workspace, workspace_bytes,
-                                          static_cast<hipStream_t>(stream));
+                                          device_form(stream).stream);
 }
 
 namespace {
@@ -1861,17 +1860,11 @@ struct transcript_columns_inputs {
 transcript_columns_inputs transcript_columns_form_inputs(
     const char* name, const void* polynomials, const void* evaluation_point, const void* transcript,
     const struct bzamd_sumcheck_columns* columns) {
-  if (polynomials == nullptr || evaluation_point == nullptr || columns == nullptr ||
-      transcript == nullptr) {
-    std::fprintf(stderr, "blitzar_amd: null argument to `%s`\n", name);
-    std::abort();
-  }
+  check_arguments(name, polynomials != nullptr && evaluation_point != nullptr &&
+                            columns != nullptr && transcript != nullptr);
   BZ_RELEASE_ASSERT(columns->product_table != nullptr && columns->product_terms != nullptr,
                     "null table in the sumcheck descriptor");
-  return {proof::sumcheck_inputs{nullptr, columns->product_table, columns->product_terms, columns->n,
-                                 columns->num_mles, columns->num_products,
-                                 columns->num_product_terms, columns->round_degree},
-          checked_sumcheck_columns(columns)};
+  return {inputs_of(*columns), checked_sumcheck_columns(columns)};
 }
 } // namespace
 
@@ -1891,10 +1884,7 @@ void bzamd_prove_sumcheck_transcript_columns(void* polynomials, void* evaluation
 uint64_t bzamd_sumcheck_transcript_columns_workspace_bytes(
     unsigned field_id, const struct bzamd_sumcheck_columns* columns) {
   BZ_RELEASE_ASSERT(columns != nullptr, "columns must not be null");
-  const proof::sumcheck_inputs in{nullptr, nullptr, nullptr, columns->n, columns->num_mles,
-                                  columns->num_products, columns->num_product_terms,
-                                  columns->round_degree};
-  return proof::sumcheck_transcript_columns_workspace_bytes(field_id, in);
+  return proof::sumcheck_transcript_columns_workspace_bytes(field_id, inputs_of(*columns, false));
 }
 
 void bzamd_prove_sumcheck_transcript_device_columns(void* polynomials, void* evaluation_point,
@@ -1906,13 +1896,10 @@ void bzamd_prove_sumcheck_transcript_device_columns(void* polynomials, void* eva
   const transcript_columns_inputs c =
       transcript_columns_form_inputs("bzamd_prove_sumcheck_transcript_device_columns", polynomials,
                                      evaluation_point, transcript, columns);
-  // as bzamd_prove_sumcheck_transcript_device: the current device, the caller's stream and
-  // workspace, no lease
-  BZ_RELEASE_ASSERT(state().backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
   proof::prove_sumcheck_transcript_device_columns(polynomials, evaluation_point, mle_evaluations,
                                                   transcript, field_id, c.in, c.cols.data(),
                                                   workspace, workspace_bytes,
-                                                  static_cast<hipStream_t>(stream));
+                                                  device_form(stream).stream);
 }
 
 int bzamd_verify_sumcheck(void* expected_sum, void* evaluation_point,

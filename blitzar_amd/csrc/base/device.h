@@ -1,6 +1,6 @@
 // Minimal HIP runtime plumbing for the engine: loud error checks (the C ABI of the reference has
 // no error channel -- sxt/base/error/panic.h:68-79 aborts on every CUDA error, and so do we),
-// a grow-only device arena, and device discovery.
+// a grow-only device arena, the carver of a caller's workspace, and device discovery.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -93,6 +93,28 @@ private:
   void* base_ = nullptr;
   size_t capacity_ = 0;
   size_t used_ = 0;
+};
+
+// Carves a caller's device workspace, whose pointer may have any alignment, into regions at
+// multiples of 256 bytes: take() hands out offsets from aligned(workspace), total() is what the
+// caller has to bring.
+class workspace_carver {
+public:
+  size_t take(size_t bytes) {
+    const size_t here = at_;
+    at_ += device_arena::padded(bytes);
+    return here;
+  }
+  // the end of the last region, and with whatever the caller's pointer lacks to a multiple of 256
+  size_t end() const { return at_; }
+  size_t total() const { return at_ + 256; }
+  static u8* aligned(void* workspace) {
+    const uintptr_t address = reinterpret_cast<uintptr_t>(workspace);
+    return static_cast<u8*>(workspace) + (256 - address % 256) % 256;
+  }
+
+private:
+  size_t at_ = 0;
 };
 
 // Pinned host staging for small per-call descriptor arrays that are uploaded with hipMemcpyAsync:

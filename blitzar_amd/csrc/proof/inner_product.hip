@@ -268,21 +268,16 @@ u64 ceil_log2(u64 n) {
 struct workspace_layout {
   size_t scalars, b, generators, terms, partials, slot, q, lr, total;
   explicit workspace_layout(u64 np) {
-    size_t at = 0;
-    auto take = [&at](size_t bytes) {
-      const size_t here = at;
-      at += device_arena::padded(bytes);
-      return here;
-    };
-    scalars = take(32 * (np + 2));
-    b = take(32 * np);
-    generators = take(sizeof(ed_point) * (np + 1));
-    terms = take(sizeof(ed29_cached_packed) * 3 * (np / 2));
-    partials = take(sizeof(s25::fe) * 2 * kPartialBlocks);
-    slot = take(sizeof(fold_slot));
-    q = take(sizeof(ed_point));
-    lr = take(64);
-    total = at + 256; // whatever the caller's pointer lacks to a multiple of 256
+    workspace_carver carve;
+    scalars = carve.take(32 * (np + 2));
+    b = carve.take(32 * np);
+    generators = carve.take(sizeof(ed_point) * (np + 1));
+    terms = carve.take(sizeof(ed29_cached_packed) * 3 * (np / 2));
+    partials = carve.take(sizeof(s25::fe) * 2 * kPartialBlocks);
+    slot = carve.take(sizeof(fold_slot));
+    q = carve.take(sizeof(ed_point));
+    lr = carve.take(64);
+    total = carve.total();
   }
 };
 
@@ -299,8 +294,7 @@ void enqueue_chain(msm_context& ctx, u8* l_vector, u8* r_vector, u8* ap_value, u
   const workspace_layout layout{np};
   BZ_RELEASE_ASSERT(workspace != nullptr && workspace_bytes >= layout.total,
                     "the inner-product workspace is too small");
-  const uintptr_t address = reinterpret_cast<uintptr_t>(workspace);
-  u8* base = static_cast<u8*>(workspace) + (256 - address % 256) % 256;
+  u8* base = workspace_carver::aligned(workspace);
   u64* d_s = reinterpret_cast<u64*>(base + layout.scalars);
   u64* d_a = d_s + 4; // behind the c_l row
   u64* d_b = reinterpret_cast<u64*>(base + layout.b);
@@ -681,19 +675,14 @@ __global__ void __launch_bounds__(64)
 struct verify_layout {
   size_t generators, scalars, b, partials, slot, encodings, total;
   verify_layout(u64 np, u64 rounds) {
-    size_t at = 0;
-    auto take = [&at](size_t bytes) {
-      const size_t here = at;
-      at += device_arena::padded(bytes);
-      return here;
-    };
-    generators = take(sizeof(ed_point) * (2 + np + 2 * rounds));
-    scalars = take(32 * (kVerifyRowG + np + 2 * rounds));
-    b = take(32 * np);
-    partials = take(sizeof(s25::fe) * kPartialBlocks);
-    slot = take(sizeof(verify_slot));
-    encodings = take(64);
-    total = at + 256; // whatever the caller's pointer lacks to a multiple of 256
+    workspace_carver carve;
+    generators = carve.take(sizeof(ed_point) * (2 + np + 2 * rounds));
+    scalars = carve.take(32 * (kVerifyRowG + np + 2 * rounds));
+    b = carve.take(32 * np);
+    partials = carve.take(sizeof(s25::fe) * kPartialBlocks);
+    slot = carve.take(sizeof(verify_slot));
+    encodings = carve.take(64);
+    total = carve.total();
   }
 };
 
@@ -706,8 +695,7 @@ void enqueue_verify_chain(msm_context& ctx, u32* verdict, u8* transcript, u64 n,
   const verify_layout layout{np, rounds};
   BZ_RELEASE_ASSERT(workspace != nullptr && workspace_bytes >= layout.total,
                     "the inner-product verifier's workspace is too small");
-  const uintptr_t address = reinterpret_cast<uintptr_t>(workspace);
-  u8* base = static_cast<u8*>(workspace) + (256 - address % 256) % 256;
+  u8* base = workspace_carver::aligned(workspace);
   ed_point* d_g = reinterpret_cast<ed_point*>(base + layout.generators);
   u8* d_s = base + layout.scalars;
   u64* d_e = reinterpret_cast<u64*>(d_s + 32 * kVerifyRowG);

@@ -48,46 +48,23 @@ __global__ void __launch_bounds__(256)
   if (i < count) out[i] = E::load(elements + E::element_bytes * i);
 }
 
-// partials[block][k] = the block's share of coefficient k of the round polynomial
-// round_degree D <= kFixedDegree: no array is indexed at run time (no scratch memory)
+// the round kernels on engine-form tables (the bodies: proof/sumcheck_rows.h)
 template <class F, u32 D>
 __global__ void __launch_bounds__(kRoundThreads)
     k_sumcheck_round_fixed(typename F::fe* __restrict__ partials,
                            const typename F::fe* __restrict__ mles, u64 n, u64 mid,
                            const product_desc<F>* __restrict__ products, u32 num_products,
                            const u32* __restrict__ terms) {
-  using fe = typename F::fe;
-  __shared__ fe tree[D + 1][kRoundThreads];
-  fe poly[D + 1];
-#pragma unroll
-  for (u32 k = 0; k <= D; ++k) poly[k] = F::zero();
-  const dense_tables<F> tables{mles, n, mid};
-  for (u64 i = static_cast<u64>(blockIdx.x) * kRoundThreads + threadIdx.x; i < mid;
-       i += static_cast<u64>(gridDim.x) * kRoundThreads) {
-    accumulate_row_fixed<F, D>(poly, tables, i, products, num_products, terms);
-  }
-  store_partials<F, D>(partials + static_cast<u64>(blockIdx.x) * (kMaxDegree + 1), tree, poly);
+  round_fixed_body<F, D>(partials, dense_tables<F>{mles, n, mid}, products, num_products, terms);
 }
-
-// round_degree 6 .. 8: product lengths at run time (p[] and poly[] live in scratch memory)
 template <class F>
 __global__ void __launch_bounds__(kRoundThreads)
     k_sumcheck_round(typename F::fe* __restrict__ partials, const typename F::fe* __restrict__ mles,
                      u64 n, u64 mid, const product_desc<F>* __restrict__ products, u32 num_products,
                      const u32* __restrict__ terms, u32 degree) {
-  using fe = typename F::fe;
-  __shared__ fe tree[kRoundThreads];
-  fe poly[kMaxDegree + 1];
-  for (u32 k = 0; k <= kMaxDegree; ++k) poly[k] = F::zero();
-  const dense_tables<F> tables{mles, n, mid};
-  for (u64 i = static_cast<u64>(blockIdx.x) * kRoundThreads + threadIdx.x; i < mid;
-       i += static_cast<u64>(gridDim.x) * kRoundThreads) {
-    accumulate_row<F>(poly, tables, i, products, num_products, terms);
-  }
-  for (u32 k = 0; k <= degree; ++k) {
-    const fe sum = block_sum<F>(tree, poly[k]);
-    if (threadIdx.x == 0) partials[static_cast<u64>(blockIdx.x) * (kMaxDegree + 1) + k] = sum;
-  }
+  typename F::fe poly[kMaxDegree + 1];
+  round_generic_body<F>(partials, poly, dense_tables<F>{mles, n, mid}, products, num_products,
+                        terms, degree);
 }
 
 // poly[k] = sum_blocks partials[block][k]: workgroup k adds up coefficient k
@@ -106,17 +83,14 @@ __global__ void __launch_bounds__(kRoundThreads)
   if (threadIdx.x == 0) poly[k] = sum;
 }
 
-// out[m * mid + i] = (1 - r) in[m * n + i] + r in[m * n + mid + i]  (cpu_driver.h:106-143)
+// out[m * mid + i] = (1 - r) in[m * n + i] + r in[m * n + mid + i]
 template <class F>
 __global__ void __launch_bounds__(256)
     k_sumcheck_fold(typename F::fe* __restrict__ out, const typename F::fe* __restrict__ in, u64 n,
                     u64 mid, u32 num_mles, typename F::fe r, typename F::fe one_minus_r) {
   const u64 id = static_cast<u64>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (id >= mid * num_mles) return;
-  const u64 m = id / mid, i = id % mid;
-  typename F::fe v = F::mul(in[m * n + i], one_minus_r);
-  if (mid + i < n) v = fadd<F>(v, F::mul(r, in[m * n + mid + i]));
-  out[id] = v;
+  out[id] = fold_element<F, u64>(in, n, mid, id / mid, id % mid, r, one_minus_r);
 }
 
 //--------------------------------------------------------------------------------------------------
@@ -193,9 +167,7 @@ void prove(api_state& st, u8* polynomials, u8* evaluation_point, u8* mle_evaluat
   const u32 degree = d.round_degree;
   const u32 length = degree + 1;
   u64 n = d.n;
-  u32 num_variables = 0;
-  while ((u64{1} << num_variables) < n) ++num_variables;
-  if (num_variables == 0) num_variables = 1;
+  const u32 num_variables = variables_of(n);
 
   const std::vector<product_desc<F>> products = engine_products<E>(d);
 
@@ -276,7 +248,7 @@ void prove(api_state& st, u8* polynomials, u8* evaluation_point, u8* mle_evaluat
     const u64 mid = u64{1} << (num_variables - 1 - round);
     std::vector<fe> poly(kMaxDegree + 1, F::zero());
     if (on_device) {
-      const u32 blocks = static_cast<u32>(std::min<u64>(kRoundBlocks, (mid + kRoundThreads - 1) / kRoundThreads));
+      const u32 blocks = round_blocks(mid);
       if (source != nullptr && round == 0) {
         source->round(stream, blocks, d_partials, mid, d_terms, degree);
       } else {
@@ -326,9 +298,7 @@ void prove(api_state& st, u8* polynomials, u8* evaluation_point, u8* mle_evaluat
       h_next.assign(mid * d.num_mles, F::zero());
       for (u64 m = 0; m < d.num_mles; ++m) {
         for (u64 i = 0; i < mid; ++i) {
-          fe v = F::mul(h_mles[m * n + i], one_minus_r);
-          if (mid + i < n) v = fadd<F>(v, F::mul(r, h_mles[m * n + mid + i]));
-          h_next[m * mid + i] = v;
+          h_next[m * mid + i] = fold_element<F, u64>(h_mles.data(), n, mid, m, i, r, one_minus_r);
         }
       }
       h_mles.swap(h_next);
@@ -370,16 +340,10 @@ void prove_sumcheck(api_state& st, void* polynomials, void* evaluation_point, vo
                     unsigned field_id, const sumcheck_inputs& d, void* callback, void* context,
                     api_state::device_lease* lease, const sumcheck_device_tables* device_tables) {
   check_sumcheck_limits(d);
-  if (field_id == 0) {
-    prove<scalar25519_elements>(st, static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
-                                static_cast<u8*>(mle_evaluations), d, callback, context, lease,
-                                device_tables, nullptr);
-  } else if (field_id == 1) {
-    prove<grumpkin_elements>(st, static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
-                             static_cast<u8*>(mle_evaluations), d, callback, context, lease,
-                             device_tables, nullptr);
-  } else {
-    BZ_RELEASE_ASSERT(false, "unsupported field id");
-  }
+  with_elements(field_id, [&](auto elements) {
+    prove<decltype(elements)>(st, static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
+                              static_cast<u8*>(mle_evaluations), d, callback, context, lease,
+                              device_tables, nullptr);
+  });
 }
 } // namespace bz::proof

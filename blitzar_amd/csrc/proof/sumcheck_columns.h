@@ -1,15 +1,16 @@
 // What the provers over typed columns share (proof/sumcheck_columns.hip: the callback form;
 // proof/sumcheck_transcript.hip: the chain with the built-in transcript): how a column is described
 // to a kernel, how an element is fetched as the raw residue of its bytes, round 0's `Tables` over
-// the columns and the round-0 kernels.  Why raw residues are enough is in the head comment of
-// proof/sumcheck_columns.hip.  Everything has internal linkage: each translation unit compiles
-// the kernels it launches.
+// the columns, the first fold of one element, and what both forms prepare on the host (views,
+// multipliers scaled by conversion constants, the length check).  Why raw residues are enough is
+// in the head comment of proof/sumcheck_columns.hip.  The round-0 kernels are compiled once, in
+// proof/sumcheck_columns.hip, and reached through launch_sumcheck_columns_round; the small loaders
+// are inline, for the kernels of either translation unit that read a column.
 #pragma once
 
 #include "blitzar_amd/csrc/proof/sumcheck_rows.h"
 
 namespace bz::proof {
-namespace {
 // how an element's bytes are fetched (the same for a whole column: uniform over a wavefront)
 enum : u32 {
   kAccessBytes = 0, // any width, any address
@@ -22,7 +23,7 @@ struct column_view {
   u32 nbytes, access, is_signed, reserved;
 };
 
-u32 access_of(const void* data, u32 nbytes) {
+inline u32 access_of(const void* data, u32 nbytes) {
   return nbytes % 8 == 0 && reinterpret_cast<uintptr_t>(data) % 8 == 0 ? kAccessWords : kAccessBytes;
 }
 
@@ -109,68 +110,56 @@ template <class F> struct column_tables {
   }
 };
 
-//--------------------------------------------------------------------------------------------------
-// device kernels
-//--------------------------------------------------------------------------------------------------
-// round 0, round_degree D <= kFixedDegree: k_sumcheck_round_fixed's expansion (no scratch memory);
-// `products`: the multipliers times their terms' conversion constants
-template <class F, u32 D>
-__global__ void __launch_bounds__(kRoundThreads)
-    k_sumcheck_columns_round(typename F::fe* __restrict__ partials,
-                             const column_view* __restrict__ views, u64 mid,
-                             const product_desc<F>* __restrict__ products, u32 num_products,
-                             const u32* __restrict__ terms) {
-  using fe = typename F::fe;
-  __shared__ fe tree[D + 1][kRoundThreads];
-  fe poly[D + 1];
-#pragma unroll
-  for (u32 k = 0; k <= D; ++k) poly[k] = F::zero();
-  const column_tables<F> tables{views, mid};
-  for (u64 i = static_cast<u64>(blockIdx.x) * kRoundThreads + threadIdx.x; i < mid;
-       i += static_cast<u64>(gridDim.x) * kRoundThreads) {
-    accumulate_row_fixed<F, D>(poly, tables, i, products, num_products, terms);
-  }
-  store_partials<F, D>(partials + static_cast<u64>(blockIdx.x) * (kMaxDegree + 1), tree, poly);
+// The first fold, one output element in engine form from raw rows; rows past the column's end are
+// zero.  r() and one_minus_r(): the challenge and its complement times the conversion constant of
+// the column's kind, asked for only where a row exists (each fold kernel has its own way of
+// obtaining them, and keeps it where it was: inside the branch)
+template <class F, class R, class OneMinusR>
+BZ_HD typename F::fe fold_column_element(const column_view& c, u64 mid, u64 i, const R& r,
+                                         const OneMinusR& one_minus_r) {
+  typename F::fe v = F::zero();
+  if (i < c.n) v = F::mul(load_raw<F>(c, i), one_minus_r());
+  if (mid + i < c.n) v = fadd<F>(v, F::mul(r(), load_raw<F>(c, mid + i)));
+  return v;
 }
 
-// round 0, round_degree 6 .. 8: product lengths at run time
+//--------------------------------------------------------------------------------------------------
+// host side
+//--------------------------------------------------------------------------------------------------
+inline column_view make_column_view(const sumcheck_column& c) {
+  return column_view{static_cast<const u8*>(c.data), c.n, c.nbytes, access_of(c.data, c.nbytes),
+                     c.is_signed ? 1u : 0u, 0};
+}
+
+// out[p] = products[p] with its multiplier times the conversion constants of its terms' columns:
+// what round 0 on raw rows takes
+template <class E>
+void conversion_scaled_products(product_desc<typename E::F>* out,
+                                const product_desc<typename E::F>* products, u32 num_products,
+                                const u32* terms, const column_view* views) {
+  using F = typename E::F;
+  for (u32 p = 0; p < num_products; ++p) {
+    product_desc<F> raw = products[p];
+    for (u32 t = 0; t < raw.num_terms; ++t) {
+      const column_view& c = views[terms[raw.first_term + t]];
+      raw.multiplier = F::mul(raw.multiplier, E::conversion(c.nbytes == E::element_bytes));
+    }
+    out[p] = raw;
+  }
+}
+
+inline void check_column_lengths(const sumcheck_inputs& d, const sumcheck_column* columns) {
+  for (u32 j = 0; j < d.num_mles; ++j) {
+    BZ_RELEASE_ASSERT(columns[j].n <= d.n, "a sumcheck column is longer than n");
+  }
+}
+
+// round 0 on the columns, enqueued on `stream` (kernels of proof/sumcheck_columns.hip):
+// partials[block][k] as the round kernels of proof/sumcheck.hip leave them; `products`: the
+// conversion-scaled ones
 template <class F>
-__global__ void __launch_bounds__(kRoundThreads)
-    k_sumcheck_columns_generic(typename F::fe* __restrict__ partials,
-                               const column_view* __restrict__ views, u64 mid,
-                               const product_desc<F>* __restrict__ products, u32 num_products,
-                               const u32* __restrict__ terms, u32 degree) {
-  using fe = typename F::fe;
-  __shared__ fe tree[kRoundThreads];
-  fe poly[kMaxDegree + 1];
-  for (u32 k = 0; k <= kMaxDegree; ++k) poly[k] = F::zero();
-  const column_tables<F> tables{views, mid};
-  for (u64 i = static_cast<u64>(blockIdx.x) * kRoundThreads + threadIdx.x; i < mid;
-       i += static_cast<u64>(gridDim.x) * kRoundThreads) {
-    accumulate_row<F>(poly, tables, i, products, num_products, terms);
-  }
-  for (u32 k = 0; k <= degree; ++k) {
-    const fe sum = block_sum<F>(tree, poly[k]);
-    if (threadIdx.x == 0) partials[static_cast<u64>(blockIdx.x) * (kMaxDegree + 1) + k] = sum;
-  }
-}
-
-template <class F, u32 D>
-void launch_columns_round(hipStream_t stream, u32 blocks, typename F::fe* d_partials,
-                          const column_view* d_views, u64 mid, const product_desc<F>* d_products,
-                          u32 num_products, const u32* d_terms, u32 degree) {
-  if (degree == D) {
-    hipLaunchKernelGGL((k_sumcheck_columns_round<F, D>), dim3(blocks), dim3(kRoundThreads), 0,
-                       stream, d_partials, d_views, mid, d_products, num_products, d_terms);
-    return;
-  }
-  if constexpr (D < kFixedDegree) {
-    launch_columns_round<F, D + 1>(stream, blocks, d_partials, d_views, mid, d_products,
-                                   num_products, d_terms, degree);
-  } else {
-    hipLaunchKernelGGL((k_sumcheck_columns_generic<F>), dim3(blocks), dim3(kRoundThreads), 0,
-                       stream, d_partials, d_views, mid, d_products, num_products, d_terms, degree);
-  }
-}
-} // namespace
+void launch_sumcheck_columns_round(hipStream_t stream, u32 blocks, typename F::fe* partials,
+                                   const column_view* views, u64 mid,
+                                   const product_desc<F>* products, u32 num_products,
+                                   const u32* terms, u32 degree);
 } // namespace bz::proof

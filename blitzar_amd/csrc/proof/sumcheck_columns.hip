@@ -3,9 +3,9 @@
 // or 32-byte field elements, each with its own length -- described by the MSM's descriptors.
 //
 // The prover is the one of proof/sumcheck.hip.  What differs is where round 0 and the first fold
-// read: the columns where they lie (k_sumcheck_columns_round, k_sumcheck_columns_generic of
-// proof/sumcheck_columns.h, shared with the chain of proof/sumcheck_transcript.hip, and
-// k_sumcheck_columns_fold).  No engine-form copy of the full tables exists on the device; from
+// read: the columns where they lie (k_sumcheck_columns_round, k_sumcheck_columns_generic, which
+// the chain of proof/sumcheck_transcript.hip launches too, through launch_sumcheck_columns_round,
+// and k_sumcheck_columns_fold).  No engine-form copy of the full tables exists on the device; from
 // round 1 on the kernels of proof/sumcheck.hip run on the folded half.
 //
 // Neither kernel converts an element.  With R the engine's Montgomery radix, a loaded element is
@@ -34,8 +34,48 @@ template <class E> typename E::F::fe load_element(const column_view& c, u64 i) {
 }
 
 //--------------------------------------------------------------------------------------------------
-// device kernels (round 0: proof/sumcheck_columns.h)
+// device kernels
 //--------------------------------------------------------------------------------------------------
+// round 0 (the bodies: proof/sumcheck_rows.h); `products`: the multipliers times their terms'
+// conversion constants.  round_degree D <= kFixedDegree: k_sumcheck_round_fixed's expansion
+template <class F, u32 D>
+__global__ void __launch_bounds__(kRoundThreads)
+    k_sumcheck_columns_round(typename F::fe* __restrict__ partials,
+                             const column_view* __restrict__ views, u64 mid,
+                             const product_desc<F>* __restrict__ products, u32 num_products,
+                             const u32* __restrict__ terms) {
+  round_fixed_body<F, D>(partials, column_tables<F>{views, mid}, products, num_products, terms);
+}
+// round_degree 6 .. 8: product lengths at run time
+template <class F>
+__global__ void __launch_bounds__(kRoundThreads)
+    k_sumcheck_columns_generic(typename F::fe* __restrict__ partials,
+                               const column_view* __restrict__ views, u64 mid,
+                               const product_desc<F>* __restrict__ products, u32 num_products,
+                               const u32* __restrict__ terms, u32 degree) {
+  typename F::fe poly[kMaxDegree + 1];
+  round_generic_body<F>(partials, poly, column_tables<F>{views, mid}, products, num_products,
+                        terms, degree);
+}
+
+template <class F, u32 D>
+void launch_columns_round(hipStream_t stream, u32 blocks, typename F::fe* d_partials,
+                          const column_view* d_views, u64 mid, const product_desc<F>* d_products,
+                          u32 num_products, const u32* d_terms, u32 degree) {
+  if (degree == D) {
+    hipLaunchKernelGGL((k_sumcheck_columns_round<F, D>), dim3(blocks), dim3(kRoundThreads), 0,
+                       stream, d_partials, d_views, mid, d_products, num_products, d_terms);
+    return;
+  }
+  if constexpr (D < kFixedDegree) {
+    launch_columns_round<F, D + 1>(stream, blocks, d_partials, d_views, mid, d_products,
+                                   num_products, d_terms, degree);
+  } else {
+    hipLaunchKernelGGL((k_sumcheck_columns_generic<F>), dim3(blocks), dim3(kRoundThreads), 0,
+                       stream, d_partials, d_views, mid, d_products, num_products, d_terms, degree);
+  }
+}
+
 // r and 1 - r times the conversion constant of integers and of elements
 template <class F> struct fold_factors {
   typename F::fe r[2], one_minus_r[2];
@@ -50,14 +90,9 @@ __global__ void __launch_bounds__(256)
   const u64 m = id / mid, i = id % mid;
   const column_view c = views[m];
   const bool element = c.nbytes == 32;
-  typename F::fe v = F::zero();
-  if (i < c.n) {
-    v = F::mul(load_raw<F>(c, i), F::select(factors.one_minus_r[0], factors.one_minus_r[1], element));
-  }
-  if (mid + i < c.n) {
-    v = fadd<F>(v, F::mul(F::select(factors.r[0], factors.r[1], element), load_raw<F>(c, mid + i)));
-  }
-  out[id] = v;
+  out[id] = fold_column_element<F>(
+      c, mid, i, [&] { return F::select(factors.r[0], factors.r[1], element); },
+      [&] { return F::select(factors.one_minus_r[0], factors.one_minus_r[1], element); });
 }
 
 //--------------------------------------------------------------------------------------------------
@@ -69,21 +104,12 @@ public:
 
   column_source(const sumcheck_column* columns, u32 num_mles, bool upload)
       : views_(num_mles), upload_(upload) {
-    for (u32 j = 0; j < num_mles; ++j) {
-      const sumcheck_column& c = columns[j];
-      views_[j] = column_view{static_cast<const u8*>(c.data), c.n, c.nbytes,
-                              access_of(c.data, c.nbytes), c.is_signed ? 1u : 0u, 0};
-    }
+    for (u32 j = 0; j < num_mles; ++j) views_[j] = make_column_view(columns[j]);
   }
 
   void bind(const product_desc<F>* products, u32 num_products, const u32* terms) override {
-    products_.assign(products, products + num_products);
-    for (product_desc<F>& p : products_) {
-      for (u32 t = 0; t < p.num_terms; ++t) {
-        const column_view& c = views_[terms[p.first_term + t]];
-        p.multiplier = F::mul(p.multiplier, E::conversion(c.nbytes == E::element_bytes));
-      }
-    }
+    products_.resize(num_products);
+    conversion_scaled_products<E>(products_.data(), products, num_products, terms, views_.data());
   }
 
   size_t device_bytes() const override {
@@ -118,8 +144,8 @@ public:
 
   void round(hipStream_t stream, u32 blocks, fe* partials, u64 mid, const u32* terms,
              u32 degree) override {
-    launch_columns_round<F, 1>(stream, blocks, partials, d_views_, mid, d_products_,
-                               static_cast<u32>(products_.size()), terms, degree);
+    launch_sumcheck_columns_round<F>(stream, blocks, partials, d_views_, mid, d_products_,
+                                     static_cast<u32>(products_.size()), terms, degree);
   }
 
   void fold(hipStream_t stream, fe* out, u64 mid, const fe& r, const fe& one_minus_r) override {
@@ -148,16 +174,25 @@ private:
   bool upload_;
 };
 
-template <class E>
-void prove_columns(api_state& st, void* polynomials, void* evaluation_point, void* mle_evaluations,
-                   const sumcheck_inputs& d, const sumcheck_column* columns, void* callback,
-                   void* context, api_state::device_lease* lease,
-                   const sumcheck_device_tables* device_tables) {
-  column_source<E> source(columns, d.num_mles, st.backend == 2 && device_tables == nullptr);
-  prove<E>(st, static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
-           static_cast<u8*>(mle_evaluations), d, callback, context, lease, device_tables, &source);
-}
 } // namespace
+
+// round 0 for the chain of proof/sumcheck_transcript.hip as well
+template <class F>
+void launch_sumcheck_columns_round(hipStream_t stream, u32 blocks, typename F::fe* partials,
+                                   const column_view* views, u64 mid,
+                                   const product_desc<F>* products, u32 num_products,
+                                   const u32* terms, u32 degree) {
+  launch_columns_round<F, 1>(stream, blocks, partials, views, mid, products, num_products, terms,
+                             degree);
+}
+template void launch_sumcheck_columns_round<scalar25_field>(hipStream_t, u32, scalar25_field::fe*,
+                                                            const column_view*, u64,
+                                                            const product_desc<scalar25_field>*,
+                                                            u32, const u32*, u32);
+template void launch_sumcheck_columns_round<grumpkin_fq29>(hipStream_t, u32, grumpkin_fq29::fe*,
+                                                           const column_view*, u64,
+                                                           const product_desc<grumpkin_fq29>*, u32,
+                                                           const u32*, u32);
 
 void prove_sumcheck_columns(api_state& st, void* polynomials, void* evaluation_point,
                             void* mle_evaluations, unsigned field_id, const sumcheck_inputs& d,
@@ -165,17 +200,13 @@ void prove_sumcheck_columns(api_state& st, void* polynomials, void* evaluation_p
                             api_state::device_lease* lease,
                             const sumcheck_device_tables* device_tables) {
   check_sumcheck_limits(d);
-  for (u32 j = 0; j < d.num_mles; ++j) {
-    BZ_RELEASE_ASSERT(columns[j].n <= d.n, "a sumcheck column is longer than n");
-  }
-  if (field_id == 0) {
-    prove_columns<scalar25519_elements>(st, polynomials, evaluation_point, mle_evaluations, d,
-                                        columns, callback, context, lease, device_tables);
-  } else if (field_id == 1) {
-    prove_columns<grumpkin_elements>(st, polynomials, evaluation_point, mle_evaluations, d, columns,
-                                     callback, context, lease, device_tables);
-  } else {
-    BZ_RELEASE_ASSERT(false, "unsupported field id");
-  }
+  check_column_lengths(d, columns);
+  with_elements(field_id, [&](auto elements) {
+    using E = decltype(elements);
+    column_source<E> source(columns, d.num_mles, st.backend == 2 && device_tables == nullptr);
+    prove<E>(st, static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
+             static_cast<u8*>(mle_evaluations), d, callback, context, lease, device_tables,
+             &source);
+  });
 }
 } // namespace bz::proof

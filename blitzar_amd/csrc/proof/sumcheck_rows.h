@@ -1,9 +1,13 @@
-// What the translation units of the sumcheck prover share (proof/sumcheck.hip: the prover and the
-// kernels on engine-form tables; proof/sumcheck_columns.hip: round 0 and the first fold on typed
-// columns): the two fields' element conversions, the row arithmetic of a round, written once over
-// a `Tables` type that says where a row's a_j and b_j come from, and the workgroup reductions.
+// What the translation units of the sumcheck provers share (proof/sumcheck.hip: the prover with the
+// caller's transcript and the kernels on engine-form tables; proof/sumcheck_columns.hip: round 0
+// and the first fold on typed columns; proof/sumcheck_transcript.hip: the chain with the built-in
+// transcript): the two fields' element conversions and the dispatch on the field id, the shape of a
+// proof (variables, round workgroups), the row arithmetic of a round and the bodies of the round
+// kernels, written once over a `Tables` type that says where a row's a_j and b_j come from, the
+// workgroup reductions, and the fold of one element of engine-form tables.
 #pragma once
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -62,6 +66,24 @@ struct grumpkin_elements {
     return F::mul(F::from_words(w), conversion(element));
   }
 };
+
+// fn(elements) for the field's conversions (blitzar_api.h SXT_FIELD_*): the one place that knows
+// which field ids exist
+template <class Fn> decltype(auto) with_elements(unsigned field_id, Fn&& fn) {
+  BZ_RELEASE_ASSERT(field_id <= 1, "unsupported field id");
+  if (field_id == 0) return fn(scalar25519_elements{});
+  return fn(grumpkin_elements{});
+}
+
+// variables of a proof over n rows, and the workgroups of a round over `mid` pairs of rows
+inline u32 variables_of(u64 n) {
+  u32 v = 0;
+  while ((u64{1} << v) < n) ++v;
+  return v == 0 ? 1 : v;
+}
+inline u32 round_blocks(u64 mid) {
+  return static_cast<u32>(std::min<u64>(kRoundBlocks, (mid + kRoundThreads - 1) / kRoundThreads));
+}
 
 template <class F> BZ_HD typename F::fe fadd(const typename F::fe& a, const typename F::fe& b) {
   return F::reduce(F::norm(F::add(a, b)));
@@ -251,6 +273,67 @@ BZ_DEV void store_partials(typename F::fe* partials, typename F::fe (*tree)[kRou
     __syncthreads();
   }
   if (threadIdx.x <= D) partials[threadIdx.x] = tree[threadIdx.x][0];
+}
+
+// The bodies of the round kernels (k_sumcheck_round_fixed and k_sumcheck_round of
+// proof/sumcheck.hip, k_sumcheck_columns_round and k_sumcheck_columns_generic of
+// proof/sumcheck_columns.hip), which differ in their `Tables` alone:
+// partials[block][k] = the block's share of coefficient k of the round polynomial.
+// round_degree D <= kFixedDegree: no array is indexed at run time (no scratch memory)
+template <class F, u32 D, class Tables>
+BZ_DEV void round_fixed_body(typename F::fe* partials, const Tables& tables,
+                             const product_desc<F>* products, u32 num_products, const u32* terms) {
+  using fe = typename F::fe;
+  __shared__ fe tree[D + 1][kRoundThreads];
+  fe poly[D + 1];
+#pragma unroll
+  for (u32 k = 0; k <= D; ++k) poly[k] = F::zero();
+  for (u64 i = static_cast<u64>(blockIdx.x) * kRoundThreads + threadIdx.x; i < tables.mid;
+       i += static_cast<u64>(gridDim.x) * kRoundThreads) {
+    accumulate_row_fixed<F, D>(poly, tables, i, products, num_products, terms);
+  }
+  store_partials<F, D>(partials + static_cast<u64>(blockIdx.x) * (kMaxDegree + 1), tree, poly);
+}
+// round_degree 6 .. 8: product lengths at run time (p[] and poly[] live in scratch memory).
+// `poly`: the kernel's own array of kMaxDegree + 1 coefficients -- declared here it would be an
+// inlined stack object with lifetime markers, which changes the kernel's register report
+template <class F, class Tables>
+BZ_DEV void round_generic_body(typename F::fe* partials, typename F::fe* poly, const Tables& tables,
+                               const product_desc<F>* products, u32 num_products, const u32* terms,
+                               u32 degree) {
+  using fe = typename F::fe;
+  __shared__ fe tree[kRoundThreads];
+  for (u32 k = 0; k <= kMaxDegree; ++k) poly[k] = F::zero();
+  for (u64 i = static_cast<u64>(blockIdx.x) * kRoundThreads + threadIdx.x; i < tables.mid;
+       i += static_cast<u64>(gridDim.x) * kRoundThreads) {
+    accumulate_row<F>(poly, tables, i, products, num_products, terms);
+  }
+  for (u32 k = 0; k <= degree; ++k) {
+    const fe sum = block_sum<F>(tree, poly[k]);
+    if (threadIdx.x == 0) partials[static_cast<u64>(blockIdx.x) * (kMaxDegree + 1) + k] = sum;
+  }
+}
+
+// The fold of engine-form tables of n rows, one output element (cpu_driver.h:106-143):
+// (1 - r) in[m n + i] + r in[m n + mid + i], rows without a partner: (1 - r) in[m n + i].
+// `Index`: the caller's own index type, so that its address arithmetic stays what it was
+template <class F, class Index>
+BZ_HD typename F::fe fold_element(const typename F::fe* in, u64 n, Index mid, Index m, Index i,
+                                  const typename F::fe& r, const typename F::fe& one_minus_r) {
+  typename F::fe v = F::mul(in[m * n + i], one_minus_r);
+  if (mid + i < n) v = fadd<F>(v, F::mul(r, in[m * n + mid + i]));
+  return v;
+}
+// where a fold kernel's element goes: to the caller's `evaluations` (not null: the last fold of a
+// chain) in the caller's representation, else to the next table
+template <class E>
+BZ_HD void store_folded(typename E::F::fe* out, u8* evaluations, u64 id,
+                        const typename E::F::fe& v) {
+  if (evaluations != nullptr) {
+    E::store(evaluations + E::element_bytes * id, v);
+  } else {
+    out[id] = v;
+  }
 }
 
 // Round 0 and the first fold from another source than engine-form tables (typed columns,

@@ -30,8 +30,10 @@
 // No engine-form copy of the full tables is made:
 //   n <= 2 kTailRows at round degree <= 5:  k_sumcheck_columns_load writes the n-row engine-form
 //     table (these proofs are tiny), k_sumcheck_tail runs every round;
-//   otherwise round 0 is k_sumcheck_columns_round / _generic on the columns with the multipliers
-//     times their terms' c, k_sumcheck_columns_challenge (k_sumcheck_challenge that also leaves
+//   otherwise round 0 is k_sumcheck_columns_round / _generic (compiled in
+//     proof/sumcheck_columns.hip, launch_sumcheck_columns_round) on the columns with the
+//     multipliers times their terms' c, k_sumcheck_columns_challenge (k_sumcheck_challenge that
+//     also leaves
 //     r c and (1 - r) c for both kinds of column in the slot: four products on one lane, not two
 //     in every lane of the fold), k_sumcheck_columns_fold_slot (raw rows times those factors:
 //     engine form); rounds >= 1 are the chain above on the folded half and quarter.
@@ -48,19 +50,12 @@
 
 #include "blitzar_amd/csrc/proof/sumcheck_columns.h"
 #include "blitzar_amd/csrc/proof/sumcheck_protocol.h"
-#include "blitzar_amd/csrc/proof/sumcheck_rows.h"
 #include "blitzar_amd/csrc/proof/transcript.h"
 
 namespace bz::proof {
 namespace {
 // pairs of rows from which on one workgroup finishes the proof
 constexpr u32 kTailRows = 256;
-
-u32 variables_of(u64 n) {
-  u32 v = 0;
-  while ((u64{1} << v) < n) ++v;
-  return v == 0 ? 1 : v;
-}
 
 //--------------------------------------------------------------------------------------------------
 // device kernels
@@ -170,14 +165,8 @@ __global__ void __launch_bounds__(256)
   using F = typename E::F;
   const u64 id = static_cast<u64>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (id >= mid * num_mles) return;
-  const u64 m = id / mid, i = id % mid;
-  typename F::fe v = F::mul(in[m * n + i], slot[1]);
-  if (mid + i < n) v = fadd<F>(v, F::mul(slot[0], in[m * n + mid + i]));
-  if (evaluations != nullptr) {
-    E::store(evaluations + E::element_bytes * id, v);
-  } else {
-    out[id] = v;
-  }
+  store_folded<E>(out, evaluations, id,
+                  fold_element<F, u64>(in, n, mid, id / mid, id % mid, slot[0], slot[1]));
 }
 
 // The n-row engine-form table of typed columns, for proofs k_sumcheck_tail runs alone:
@@ -211,14 +200,10 @@ __global__ void __launch_bounds__(256)
   const column_view c = views[m];
   // r c and (1 - r) c of the column's kind
   const typename F::fe* factors = slot + (c.nbytes == E::element_bytes ? 4 : 2);
-  typename F::fe v = F::zero();
-  if (i < c.n) v = F::mul(load_raw<F>(c, i), factors[1]);
-  if (mid + i < c.n) v = fadd<F>(v, F::mul(factors[0], load_raw<F>(c, mid + i)));
-  if (evaluations != nullptr) {
-    E::store(evaluations + E::element_bytes * id, v);
-  } else {
-    out[id] = v;
-  }
+  store_folded<E>(out, evaluations, id,
+                  fold_column_element<F>(
+                      c, mid, i, [&]() -> const typename F::fe& { return factors[0]; },
+                      [&]() -> const typename F::fe& { return factors[1]; }));
 }
 
 // Rounds first_round .. v - 1 in one workgroup (2^(v - 1 - first_round) <= kTailRows pairs of
@@ -263,9 +248,8 @@ __global__ void __launch_bounds__(kRoundThreads)
     if (last && evaluations == nullptr) break;
     const fe r = slot[0], one_minus_r = slot[1];
     for (u32 id = threadIdx.x; id < mid * num_mles; id += kRoundThreads) {
-      const u32 m = id / mid, i = id % mid;
-      fe v = F::mul(table_in[m * n + i], one_minus_r);
-      if (mid + i < n) v = fadd<F>(v, F::mul(r, table_in[m * n + mid + i]));
+      const fe v = fold_element<F, u32>(table_in, n, mid, id / mid, id % mid, r, one_minus_r);
+      // not store_folded: the choice is `last`, and sharing it changes this kernel's registers
       if (last) {
         E::store(evaluations + E::element_bytes * id, v);
       } else {
@@ -303,24 +287,35 @@ void launch_tail(hipStream_t stream, u32 degree, u8* polynomials, u8* evaluation
 //--------------------------------------------------------------------------------------------------
 // the caller's workspace
 //--------------------------------------------------------------------------------------------------
-template <class F> struct workspace_layout {
+// whether k_sumcheck_tail runs the whole proof over typed columns (on the table
+// k_sumcheck_columns_load writes)
+bool tail_only(const sumcheck_inputs& d) {
+  return d.round_degree <= kFixedDegree && (u64{1} << (variables_of(d.n) - 1)) <= kTailRows;
+}
+
+// Engine-form tables (not `columns`), or typed columns with the tail only: the n-row table and the
+// half it folds to.  Typed columns otherwise: no table at full size, the first fold's half and the
+// quarter, ping-pong.  Over columns the views, both product tables (`raw_products`: for round 0,
+// the multipliers times their terms' conversion constants) and the terms are one block, uploaded
+// with one copy, and the slot takes six elements; without, the views and raw products are empty.
+// A function of n, num_mles, num_products, num_product_terms and round_degree alone.
+template <class F> struct chain_layout {
   using fe = typename F::fe;
-  size_t table, folded, partials, slot, products, terms, total;
-  explicit workspace_layout(const sumcheck_inputs& d) {
-    const u32 v = variables_of(d.n);
-    size_t at = 256; // whatever the caller's pointer lacks to a multiple of 256
-    auto take = [&at](size_t bytes) {
-      const size_t here = at;
-      at += device_arena::padded(bytes);
-      return here;
-    };
-    table = take(sizeof(fe) * d.n * d.num_mles);
-    folded = take(sizeof(fe) * (u64{1} << (v - 1)) * d.num_mles);
-    partials = take(sizeof(fe) * kRoundBlocks * (kMaxDegree + 1));
-    slot = take(sizeof(fe) * 2);
-    products = take(sizeof(product_desc<F>) * d.num_products);
-    terms = take(sizeof(u32) * d.num_product_terms);
-    total = at;
+  size_t table, folded, partials, slot, views, raw_products, products, terms, end, total;
+  chain_layout(const sumcheck_inputs& d, bool columns) {
+    const u64 half = u64{1} << (variables_of(d.n) - 1);
+    const bool full = !columns || tail_only(d);
+    workspace_carver carve;
+    table = carve.take(sizeof(fe) * (full ? d.n : half) * d.num_mles);
+    folded = carve.take(sizeof(fe) * (full ? half : (half + 1) / 2) * d.num_mles);
+    partials = carve.take(sizeof(fe) * kRoundBlocks * (kMaxDegree + 1));
+    slot = carve.take(sizeof(fe) * (columns ? 6 : 2));
+    views = carve.take(columns ? sizeof(column_view) * d.num_mles : 0);
+    raw_products = carve.take(columns ? sizeof(product_desc<F>) * d.num_products : 0);
+    products = carve.take(sizeof(product_desc<F>) * d.num_products);
+    terms = carve.take(sizeof(u32) * d.num_product_terms);
+    end = carve.end();
+    total = carve.total();
   }
 };
 
@@ -333,42 +328,50 @@ host_stage_ring& stage_ring() {
   return *ring;
 }
 
+// what a chain writes and where it works: memory of the current device (`mle_evaluations` may be
+// null), enqueued on `stream`
+struct chain_target {
+  u8 *polynomials, *evaluation_point, *mle_evaluations, *transcript;
+  void* workspace;
+  u64 workspace_bytes;
+  hipStream_t stream;
+};
+
 // Rounds first_round .. v - 1 of the chain on engine-form tables: d_mles holds n rows per MLE (the
 // tables as round first_round reads them), d_next takes the next fold
 template <class E>
-void chain_rounds(u8* polynomials, u8* evaluation_point, u8* mle_evaluations, u8* transcript,
-                  const sumcheck_inputs& d, u32 first_round, typename E::F::fe* d_mles, u64 n,
-                  typename E::F::fe* d_next, typename E::F::fe* d_partials,
-                  typename E::F::fe* d_slot, const product_desc<typename E::F>* d_products,
-                  const u32* d_terms, hipStream_t stream) {
+void chain_rounds(const chain_target& to, const sumcheck_inputs& d, u32 first_round,
+                  typename E::F::fe* d_mles, u64 n, typename E::F::fe* d_next,
+                  typename E::F::fe* d_partials, typename E::F::fe* d_slot,
+                  const product_desc<typename E::F>* d_products, const u32* d_terms) {
   using F = typename E::F;
+  hipStream_t stream = to.stream;
   const u32 degree = d.round_degree;
   const u32 length = degree + 1;
   const u32 num_variables = variables_of(d.n);
   for (u32 round = first_round; round < num_variables; ++round) {
     const u64 mid = u64{1} << (num_variables - 1 - round);
     if (degree <= kFixedDegree && mid <= kTailRows) {
-      launch_tail<E, 1>(stream, degree, polynomials, evaluation_point, mle_evaluations, transcript,
-                        d_mles, d_next, n, d.num_mles, d_products, d.num_products, d_terms, round,
-                        num_variables);
+      launch_tail<E, 1>(stream, degree, to.polynomials, to.evaluation_point, to.mle_evaluations,
+                        to.transcript, d_mles, d_next, n, d.num_mles, d_products, d.num_products,
+                        d_terms, round, num_variables);
       BZ_HIP_CHECK(hipGetLastError());
       g_kernel_launches += 1;
       return;
     }
-    const u32 blocks =
-        static_cast<u32>(std::min<u64>(kRoundBlocks, (mid + kRoundThreads - 1) / kRoundThreads));
+    const u32 blocks = round_blocks(mid);
     launch_sumcheck_round<F>(stream, blocks, d_partials, d_mles, n, mid, d_products, d.num_products,
                              d_terms, degree);
     BZ_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL((k_sumcheck_challenge<E>), dim3(1), dim3(kRoundThreads), 0, stream,
-                       polynomials, evaluation_point, d_slot, transcript, d_partials, blocks, length,
-                       round, num_variables);
+                       to.polynomials, to.evaluation_point, d_slot, to.transcript, d_partials,
+                       blocks, length, round, num_variables);
     BZ_HIP_CHECK(hipGetLastError());
     g_kernel_launches += 2;
     const bool last = round + 1 == num_variables;
-    if (last && mle_evaluations == nullptr) return;
+    if (last && to.mle_evaluations == nullptr) return;
     hipLaunchKernelGGL((k_sumcheck_fold_slot<E>), dim3(ceil_div_u32(mid * d.num_mles, 256)),
-                       dim3(256), 0, stream, d_next, last ? mle_evaluations : nullptr, d_mles, n,
+                       dim3(256), 0, stream, d_next, last ? to.mle_evaluations : nullptr, d_mles, n,
                        mid, d.num_mles, d_slot);
     BZ_HIP_CHECK(hipGetLastError());
     g_kernel_launches += 1;
@@ -377,17 +380,15 @@ void chain_rounds(u8* polynomials, u8* evaluation_point, u8* mle_evaluations, u8
   }
 }
 
-template <class E>
-void prove_device(u8* polynomials, u8* evaluation_point, u8* mle_evaluations, u8* transcript,
-                  const sumcheck_inputs& d, void* workspace, u64 workspace_bytes, hipStream_t stream) {
+template <class E> void prove_device(const chain_target& to, const sumcheck_inputs& d) {
   using F = typename E::F;
   using fe = typename F::fe;
+  hipStream_t stream = to.stream;
   const std::vector<product_desc<F>> products = engine_products<E>(d);
-  const workspace_layout<F> layout{d};
-  BZ_RELEASE_ASSERT(workspace != nullptr && workspace_bytes >= layout.total,
+  const chain_layout<F> layout{d, false};
+  BZ_RELEASE_ASSERT(to.workspace != nullptr && to.workspace_bytes >= layout.total,
                     "the sumcheck workspace is too small");
-  const uintptr_t address = reinterpret_cast<uintptr_t>(workspace);
-  u8* base = static_cast<u8*>(workspace) + ((256 - address % 256) % 256) - 256;
+  u8* base = workspace_carver::aligned(to.workspace);
   fe* d_mles = reinterpret_cast<fe*>(base + layout.table);
   fe* d_next = reinterpret_cast<fe*>(base + layout.folded);
   fe* d_partials = reinterpret_cast<fe*>(base + layout.partials);
@@ -412,108 +413,24 @@ void prove_device(u8* polynomials, u8* evaluation_point, u8* mle_evaluations, u8
                           static_cast<u64>(d.n) * d.num_mles);
   BZ_HIP_CHECK(hipGetLastError());
   g_kernel_launches += 1;
-  chain_rounds<E>(polynomials, evaluation_point, mle_evaluations, transcript, d, 0, d_mles, d.n,
-                  d_next, d_partials, d_slot, d_products, d_terms, stream);
+  chain_rounds<E>(to, d, 0, d_mles, d.n, d_next, d_partials, d_slot, d_products, d_terms);
 }
 
-// the GPU backend's form on host operands: upload, the device chain on the primary stream,
-// download, one synchronise
+// `columns`: d.num_mles of them, data in memory of the current device, lengths checked.  No
+// engine-form copy of the full tables unless k_sumcheck_tail runs the whole proof
 template <class E>
-void prove_uploaded(api_state& st, u8* polynomials, u8* evaluation_point, u8* mle_evaluations,
-                    u8* transcript, const sumcheck_inputs& d) {
-  using F = typename E::F;
-  const int device = st.primary().device;
-  hipStream_t stream = st.primary().stream;
-  BZ_HIP_CHECK(hipSetDevice(device));
-  const u32 num_variables = variables_of(d.n);
-  const size_t raw_bytes = static_cast<size_t>(E::element_bytes) * d.n * d.num_mles;
-  const size_t poly_bytes = static_cast<size_t>(32) * (d.round_degree + 1) * num_variables;
-  const size_t point_bytes = static_cast<size_t>(32) * num_variables;
-  const size_t evaluation_bytes = static_cast<size_t>(32) * d.num_mles;
-  const workspace_layout<F> layout{d};
-  const size_t arena_bytes = device_arena::padded(raw_bytes) + device_arena::padded(poly_bytes) +
-                             device_arena::padded(point_bytes) +
-                             device_arena::padded(evaluation_bytes) + 256 + layout.total;
-  g_sumcheck_arena_bytes.store(arena_bytes);
-  device_arena own;
-  own.reset(arena_bytes, stream);
-  u8* d_raw = own.take<u8>(raw_bytes);
-  u8* d_polynomials = own.take<u8>(poly_bytes);
-  u8* d_point = own.take<u8>(point_bytes);
-  u8* d_evaluations = own.take<u8>(evaluation_bytes);
-  u8* d_transcript = own.take<u8>(sizeof(transcript_state));
-  u8* d_workspace = own.take<u8>(layout.total);
-  BZ_HIP_CHECK(hipMemcpyAsync(d_raw, d.mles, raw_bytes, hipMemcpyHostToDevice, stream));
-  BZ_HIP_CHECK(hipMemcpyAsync(d_transcript, transcript, sizeof(transcript_state),
-                              hipMemcpyHostToDevice, stream));
-  sumcheck_inputs on_device = d;
-  on_device.mles = d_raw;
-  prove_device<E>(d_polynomials, d_point, mle_evaluations != nullptr ? d_evaluations : nullptr,
-                  d_transcript, on_device, d_workspace, layout.total, stream);
-  BZ_HIP_CHECK(hipMemcpyAsync(polynomials, d_polynomials, poly_bytes, hipMemcpyDeviceToHost, stream));
-  BZ_HIP_CHECK(hipMemcpyAsync(evaluation_point, d_point, point_bytes, hipMemcpyDeviceToHost, stream));
-  if (mle_evaluations != nullptr) {
-    BZ_HIP_CHECK(hipMemcpyAsync(mle_evaluations, d_evaluations, evaluation_bytes,
-                                hipMemcpyDeviceToHost, stream));
-  }
-  BZ_HIP_CHECK(hipMemcpyAsync(transcript, d_transcript, sizeof(transcript_state),
-                              hipMemcpyDeviceToHost, stream));
-  BZ_HIP_CHECK(hipStreamSynchronize(stream));
-  own.release();
-}
-
-//--------------------------------------------------------------------------------------------------
-// the chain over typed columns
-//--------------------------------------------------------------------------------------------------
-// whether k_sumcheck_tail runs the whole proof (on the table k_sumcheck_columns_load writes)
-bool tail_only(const sumcheck_inputs& d) {
-  return d.round_degree <= kFixedDegree && (u64{1} << (variables_of(d.n) - 1)) <= kTailRows;
-}
-
-// Tail only: the n-row table and the half it folds to.  Otherwise no table at full size: the first
-// fold's half and the quarter, ping-pong.  The views, both product tables (`raw_products`: for
-// round 0, the multipliers times their terms' conversion constants) and the terms are one block,
-// uploaded with one copy.  A function of n, num_mles, num_products, num_product_terms and
-// round_degree alone.
-template <class F> struct columns_workspace_layout {
-  using fe = typename F::fe;
-  size_t table, folded, partials, slot, views, raw_products, products, terms, total;
-  explicit columns_workspace_layout(const sumcheck_inputs& d) {
-    const u64 half = u64{1} << (variables_of(d.n) - 1);
-    const bool tail = tail_only(d);
-    size_t at = 256; // whatever the caller's pointer lacks to a multiple of 256
-    auto take = [&at](size_t bytes) {
-      const size_t here = at;
-      at += device_arena::padded(bytes);
-      return here;
-    };
-    table = take(sizeof(fe) * (tail ? d.n : half) * d.num_mles);
-    folded = take(sizeof(fe) * (tail ? half : (half + 1) / 2) * d.num_mles);
-    partials = take(sizeof(fe) * kRoundBlocks * (kMaxDegree + 1));
-    slot = take(sizeof(fe) * 6);
-    views = take(sizeof(column_view) * d.num_mles);
-    raw_products = take(sizeof(product_desc<F>) * d.num_products);
-    products = take(sizeof(product_desc<F>) * d.num_products);
-    terms = take(sizeof(u32) * d.num_product_terms);
-    total = at;
-  }
-};
-
-// `columns`: d.num_mles of them, data in memory of the current device, lengths checked
-template <class E>
-void prove_device_columns(u8* polynomials, u8* evaluation_point, u8* mle_evaluations, u8* transcript,
-                          const sumcheck_inputs& d, const sumcheck_column* columns, void* workspace,
-                          u64 workspace_bytes, hipStream_t stream) {
+void prove_device_columns(const chain_target& to, const sumcheck_inputs& d,
+                          const sumcheck_column* columns) {
   using F = typename E::F;
   using fe = typename F::fe;
+  hipStream_t stream = to.stream;
   const u32 degree = d.round_degree;
   const u32 num_variables = variables_of(d.n);
   const std::vector<product_desc<F>> products = engine_products<E>(d);
-  const columns_workspace_layout<F> layout{d};
-  BZ_RELEASE_ASSERT(workspace != nullptr && workspace_bytes >= layout.total,
+  const chain_layout<F> layout{d, true};
+  BZ_RELEASE_ASSERT(to.workspace != nullptr && to.workspace_bytes >= layout.total,
                     "the sumcheck workspace is too small");
-  const uintptr_t address = reinterpret_cast<uintptr_t>(workspace);
-  u8* base = static_cast<u8*>(workspace) + ((256 - address % 256) % 256) - 256;
+  u8* base = workspace_carver::aligned(to.workspace);
   fe* d_table = reinterpret_cast<fe*>(base + layout.table);
   fe* d_folded = reinterpret_cast<fe*>(base + layout.folded);
   fe* d_partials = reinterpret_cast<fe*>(base + layout.partials);
@@ -525,24 +442,14 @@ void prove_device_columns(u8* polynomials, u8* evaluation_point, u8* mle_evaluat
 
   {
     // the block from the views to the terms, laid out in pinned memory as in the workspace
-    const size_t block_bytes = layout.total - layout.views;
+    const size_t block_bytes = layout.end - layout.views;
     const std::lock_guard<std::mutex> lock{g_stage_mutex};
     u8* staged = static_cast<u8*>(stage_ring().acquire(block_bytes));
     auto* views = reinterpret_cast<column_view*>(staged);
-    for (u32 j = 0; j < d.num_mles; ++j) {
-      const sumcheck_column& c = columns[j];
-      views[j] = column_view{static_cast<const u8*>(c.data), c.n, c.nbytes,
-                             access_of(c.data, c.nbytes), c.is_signed ? 1u : 0u, 0};
-    }
-    auto* raw_products = reinterpret_cast<product_desc<F>*>(staged + (layout.raw_products - layout.views));
-    for (u32 p = 0; p < d.num_products; ++p) {
-      product_desc<F> raw = products[p];
-      for (u32 t = 0; t < raw.num_terms; ++t) {
-        const sumcheck_column& c = columns[d.product_terms[raw.first_term + t]];
-        raw.multiplier = F::mul(raw.multiplier, E::conversion(c.nbytes == E::element_bytes));
-      }
-      raw_products[p] = raw;
-    }
+    for (u32 j = 0; j < d.num_mles; ++j) views[j] = make_column_view(columns[j]);
+    conversion_scaled_products<E>(
+        reinterpret_cast<product_desc<F>*>(staged + (layout.raw_products - layout.views)),
+        products.data(), d.num_products, d.product_terms, views);
     std::memcpy(staged + (layout.products - layout.views), products.data(),
                 sizeof(product_desc<F>) * products.size());
     std::memcpy(staged + (layout.terms - layout.views), d.product_terms,
@@ -557,39 +464,37 @@ void prove_device_columns(u8* polynomials, u8* evaluation_point, u8* mle_evaluat
                        stream, d_table, d_views, static_cast<u64>(d.n), d.num_mles);
     BZ_HIP_CHECK(hipGetLastError());
     g_kernel_launches += 1;
-    chain_rounds<E>(polynomials, evaluation_point, mle_evaluations, transcript, d, 0, d_table, d.n,
-                    d_folded, d_partials, d_slot, d_products, d_terms, stream);
+    chain_rounds<E>(to, d, 0, d_table, d.n, d_folded, d_partials, d_slot, d_products, d_terms);
     return;
   }
   const u64 mid = u64{1} << (num_variables - 1);
-  const u32 blocks =
-      static_cast<u32>(std::min<u64>(kRoundBlocks, (mid + kRoundThreads - 1) / kRoundThreads));
-  launch_columns_round<F, 1>(stream, blocks, d_partials, d_views, mid, d_raw_products,
-                             d.num_products, d_terms, degree);
+  const u32 blocks = round_blocks(mid);
+  launch_sumcheck_columns_round<F>(stream, blocks, d_partials, d_views, mid, d_raw_products,
+                                   d.num_products, d_terms, degree);
   BZ_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL((k_sumcheck_columns_challenge<E>), dim3(1), dim3(kRoundThreads), 0, stream,
-                     polynomials, evaluation_point, d_slot, transcript, d_partials, blocks,
+                     to.polynomials, to.evaluation_point, d_slot, to.transcript, d_partials, blocks,
                      degree + 1, num_variables);
   BZ_HIP_CHECK(hipGetLastError());
   g_kernel_launches += 2;
   const bool last = num_variables == 1;
-  if (last && mle_evaluations == nullptr) return;
+  if (last && to.mle_evaluations == nullptr) return;
   hipLaunchKernelGGL((k_sumcheck_columns_fold_slot<E>), dim3(ceil_div_u32(mid * d.num_mles, 256)),
-                     dim3(256), 0, stream, d_table, last ? mle_evaluations : nullptr, d_views, mid,
-                     d.num_mles, d_slot);
+                     dim3(256), 0, stream, d_table, last ? to.mle_evaluations : nullptr, d_views,
+                     mid, d.num_mles, d_slot);
   BZ_HIP_CHECK(hipGetLastError());
   g_kernel_launches += 1;
-  chain_rounds<E>(polynomials, evaluation_point, mle_evaluations, transcript, d, 1, d_table, mid,
-                  d_folded, d_partials, d_slot, d_products, d_terms, stream);
+  chain_rounds<E>(to, d, 1, d_table, mid, d_folded, d_partials, d_slot, d_products, d_terms);
 }
 
-// the GPU backend's form on host columns: upload them at their own width, the device chain on the
-// primary stream, download, one synchronise
-template <class E>
-void prove_uploaded_columns(api_state& st, u8* polynomials, u8* evaluation_point,
-                            u8* mle_evaluations, u8* transcript, const sumcheck_inputs& d,
-                            const sumcheck_column* columns) {
-  using F = typename E::F;
+// The GPU backend's forms on host operands, on the primary stream: the outputs, the transcript and
+// the chain's workspace in memory of the call's own, the transcript up, `chain(own, target)` --
+// which takes `input_bytes` more from `own`, uploads its inputs there and enqueues the device form
+// on them -- then the four results down, one synchronise
+template <class F, class Chain>
+void prove_uploaded(api_state& st, u8* polynomials, u8* evaluation_point, u8* mle_evaluations,
+                    u8* transcript, const sumcheck_inputs& d, bool columns, size_t input_bytes,
+                    Chain&& chain) {
   const int device = st.primary().device;
   hipStream_t stream = st.primary().stream;
   BZ_HIP_CHECK(hipSetDevice(device));
@@ -597,22 +502,13 @@ void prove_uploaded_columns(api_state& st, u8* polynomials, u8* evaluation_point
   const size_t poly_bytes = static_cast<size_t>(32) * (d.round_degree + 1) * num_variables;
   const size_t point_bytes = static_cast<size_t>(32) * num_variables;
   const size_t evaluation_bytes = static_cast<size_t>(32) * d.num_mles;
-  const columns_workspace_layout<F> layout{d};
-  size_t arena_bytes = device_arena::padded(poly_bytes) + device_arena::padded(point_bytes) +
-                       device_arena::padded(evaluation_bytes) + 256 + layout.total;
-  for (u32 j = 0; j < d.num_mles; ++j) {
-    arena_bytes += device_arena::padded(columns[j].n * columns[j].nbytes);
-  }
+  const chain_layout<F> layout{d, columns};
+  const size_t arena_bytes = input_bytes + device_arena::padded(poly_bytes) +
+                             device_arena::padded(point_bytes) +
+                             device_arena::padded(evaluation_bytes) + 256 + layout.total;
   g_sumcheck_arena_bytes.store(arena_bytes);
   device_arena own;
   own.reset(arena_bytes, stream);
-  std::vector<sumcheck_column> on_device(columns, columns + d.num_mles);
-  for (sumcheck_column& c : on_device) {
-    const size_t bytes = c.n * c.nbytes;
-    u8* staged = own.take<u8>(bytes);
-    if (bytes != 0) BZ_HIP_CHECK(hipMemcpyAsync(staged, c.data, bytes, hipMemcpyHostToDevice, stream));
-    c.data = staged;
-  }
   u8* d_polynomials = own.take<u8>(poly_bytes);
   u8* d_point = own.take<u8>(point_bytes);
   u8* d_evaluations = own.take<u8>(evaluation_bytes);
@@ -620,9 +516,9 @@ void prove_uploaded_columns(api_state& st, u8* polynomials, u8* evaluation_point
   u8* d_workspace = own.take<u8>(layout.total);
   BZ_HIP_CHECK(hipMemcpyAsync(d_transcript, transcript, sizeof(transcript_state),
                               hipMemcpyHostToDevice, stream));
-  prove_device_columns<E>(d_polynomials, d_point,
-                          mle_evaluations != nullptr ? d_evaluations : nullptr, d_transcript, d,
-                          on_device.data(), d_workspace, layout.total, stream);
+  chain(own, chain_target{d_polynomials, d_point,
+                          mle_evaluations != nullptr ? d_evaluations : nullptr, d_transcript,
+                          d_workspace, layout.total, stream});
   BZ_HIP_CHECK(hipMemcpyAsync(polynomials, d_polynomials, poly_bytes, hipMemcpyDeviceToHost, stream));
   BZ_HIP_CHECK(hipMemcpyAsync(evaluation_point, d_point, point_bytes, hipMemcpyDeviceToHost, stream));
   if (mle_evaluations != nullptr) {
@@ -635,10 +531,45 @@ void prove_uploaded_columns(api_state& st, u8* polynomials, u8* evaluation_point
   own.release();
 }
 
-void check_column_lengths(const sumcheck_inputs& d, const sumcheck_column* columns) {
+// host tables: uploaded as they are, converted on the device
+template <class E>
+void prove_uploaded_tables(api_state& st, u8* polynomials, u8* evaluation_point,
+                           u8* mle_evaluations, u8* transcript, const sumcheck_inputs& d) {
+  const size_t raw_bytes = static_cast<size_t>(E::element_bytes) * d.n * d.num_mles;
+  prove_uploaded<typename E::F>(
+      st, polynomials, evaluation_point, mle_evaluations, transcript, d, false,
+      device_arena::padded(raw_bytes), [&](device_arena& own, const chain_target& to) {
+        u8* d_raw = own.take<u8>(raw_bytes);
+        BZ_HIP_CHECK(hipMemcpyAsync(d_raw, d.mles, raw_bytes, hipMemcpyHostToDevice, to.stream));
+        sumcheck_inputs on_device = d;
+        on_device.mles = d_raw;
+        prove_device<E>(to, on_device);
+      });
+}
+
+// host columns: uploaded at their own width
+template <class E>
+void prove_uploaded_columns(api_state& st, u8* polynomials, u8* evaluation_point,
+                            u8* mle_evaluations, u8* transcript, const sumcheck_inputs& d,
+                            const sumcheck_column* columns) {
+  size_t column_bytes = 0;
   for (u32 j = 0; j < d.num_mles; ++j) {
-    BZ_RELEASE_ASSERT(columns[j].n <= d.n, "a sumcheck column is longer than n");
+    column_bytes += device_arena::padded(columns[j].n * columns[j].nbytes);
   }
+  prove_uploaded<typename E::F>(
+      st, polynomials, evaluation_point, mle_evaluations, transcript, d, true, column_bytes,
+      [&](device_arena& own, const chain_target& to) {
+        std::vector<sumcheck_column> on_device(columns, columns + d.num_mles);
+        for (sumcheck_column& c : on_device) {
+          const size_t bytes = c.n * c.nbytes;
+          u8* staged = own.take<u8>(bytes);
+          if (bytes != 0) {
+            BZ_HIP_CHECK(hipMemcpyAsync(staged, c.data, bytes, hipMemcpyHostToDevice, to.stream));
+          }
+          c.data = staged;
+        }
+        prove_device_columns<E>(to, d, on_device.data());
+      });
 }
 
 struct round_context {
@@ -685,50 +616,38 @@ void sumcheck_transcript_begin(void* transcript, u64 num_variables, u64 round_de
 
 void sumcheck_transcript_round(void* r, void* transcript, unsigned field_id, const void* polynomial,
                                unsigned length) {
-  auto* t = static_cast<transcript_state*>(transcript);
-  u8 x[32];
-  if (field_id == 0) {
-    transcript_round<scalar25519_elements, host_sponge>(static_cast<u8*>(r), x, t,
-                                                        static_cast<const u8*>(polynomial), length);
-  } else if (field_id == 1) {
-    transcript_round<grumpkin_elements, host_sponge>(static_cast<u8*>(r), x, t,
-                                                     static_cast<const u8*>(polynomial), length);
-  } else {
-    BZ_RELEASE_ASSERT(false, "unsupported field id");
-  }
+  with_elements(field_id, [&](auto elements) {
+    u8 x[32];
+    transcript_round<decltype(elements), host_sponge>(
+        static_cast<u8*>(r), x, static_cast<transcript_state*>(transcript),
+        static_cast<const u8*>(polynomial), length);
+  });
 }
 
 void prove_sumcheck_transcript(api_state& st, void* polynomials, void* evaluation_point,
                                void* mle_evaluations, void* transcript, unsigned field_id,
                                const sumcheck_inputs& d) {
   check_sumcheck_limits(d);
-  BZ_RELEASE_ASSERT(field_id <= 1, "unsupported field id");
-  if (st.backend != 2) {
-    // the host round loop with the host Merlin as its callback
-    sumcheck_transcript_begin(transcript, variables_of(d.n), d.round_degree);
-    round_context context{transcript, field_id};
-    prove_sumcheck(st, polynomials, evaluation_point, mle_evaluations, field_id, d,
-                   reinterpret_cast<void*>(&round_callback), &context);
-    return;
-  }
-  if (field_id == 0) {
-    prove_uploaded<scalar25519_elements>(st, static_cast<u8*>(polynomials),
-                                         static_cast<u8*>(evaluation_point),
-                                         static_cast<u8*>(mle_evaluations),
-                                         static_cast<u8*>(transcript), d);
-  } else {
-    prove_uploaded<grumpkin_elements>(st, static_cast<u8*>(polynomials),
-                                      static_cast<u8*>(evaluation_point),
-                                      static_cast<u8*>(mle_evaluations),
-                                      static_cast<u8*>(transcript), d);
-  }
+  with_elements(field_id, [&](auto elements) {
+    if (st.backend != 2) {
+      // the host round loop with the host Merlin as its callback
+      sumcheck_transcript_begin(transcript, variables_of(d.n), d.round_degree);
+      round_context context{transcript, field_id};
+      prove_sumcheck(st, polynomials, evaluation_point, mle_evaluations, field_id, d,
+                     reinterpret_cast<void*>(&round_callback), &context);
+      return;
+    }
+    prove_uploaded_tables<decltype(elements)>(
+        st, static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
+        static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript), d);
+  });
 }
 
 u64 sumcheck_transcript_workspace_bytes(unsigned field_id, const sumcheck_inputs& d) {
   check_sumcheck_limits(d);
-  BZ_RELEASE_ASSERT(field_id <= 1, "unsupported field id");
-  return field_id == 0 ? workspace_layout<scalar25_field>{d}.total
-                       : workspace_layout<grumpkin_fq29>{d}.total;
+  return with_elements(field_id, [&](auto elements) -> u64 {
+    return chain_layout<typename decltype(elements)::F>{d, false}.total;
+  });
 }
 
 void prove_sumcheck_transcript_device(void* polynomials, void* evaluation_point,
@@ -736,51 +655,40 @@ void prove_sumcheck_transcript_device(void* polynomials, void* evaluation_point,
                                       const sumcheck_inputs& d, void* workspace, u64 workspace_bytes,
                                       hipStream_t stream) {
   check_sumcheck_limits(d);
-  if (field_id == 0) {
-    prove_device<scalar25519_elements>(static_cast<u8*>(polynomials),
-                                       static_cast<u8*>(evaluation_point),
-                                       static_cast<u8*>(mle_evaluations),
-                                       static_cast<u8*>(transcript), d, workspace, workspace_bytes,
-                                       stream);
-  } else if (field_id == 1) {
-    prove_device<grumpkin_elements>(static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
-                                    static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript),
-                                    d, workspace, workspace_bytes, stream);
-  } else {
-    BZ_RELEASE_ASSERT(false, "unsupported field id");
-  }
+  with_elements(field_id, [&](auto elements) {
+    prove_device<decltype(elements)>(
+        chain_target{static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
+                     static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript), workspace,
+                     workspace_bytes, stream},
+        d);
+  });
 }
 
 void prove_sumcheck_transcript_columns(api_state& st, void* polynomials, void* evaluation_point,
                                        void* mle_evaluations, void* transcript, unsigned field_id,
                                        const sumcheck_inputs& d, const sumcheck_column* columns) {
   check_sumcheck_limits(d);
-  BZ_RELEASE_ASSERT(field_id <= 1, "unsupported field id");
-  if (st.backend != 2) {
-    // the host round loop over the columns with the host Merlin as its callback
-    sumcheck_transcript_begin(transcript, variables_of(d.n), d.round_degree);
-    round_context context{transcript, field_id};
-    prove_sumcheck_columns(st, polynomials, evaluation_point, mle_evaluations, field_id, d, columns,
-                           reinterpret_cast<void*>(&round_callback), &context);
-    return;
-  }
-  check_column_lengths(d, columns);
-  if (field_id == 0) {
-    prove_uploaded_columns<scalar25519_elements>(
+  with_elements(field_id, [&](auto elements) {
+    if (st.backend != 2) {
+      // the host round loop over the columns with the host Merlin as its callback
+      sumcheck_transcript_begin(transcript, variables_of(d.n), d.round_degree);
+      round_context context{transcript, field_id};
+      prove_sumcheck_columns(st, polynomials, evaluation_point, mle_evaluations, field_id, d,
+                             columns, reinterpret_cast<void*>(&round_callback), &context);
+      return;
+    }
+    check_column_lengths(d, columns);
+    prove_uploaded_columns<decltype(elements)>(
         st, static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
         static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript), d, columns);
-  } else {
-    prove_uploaded_columns<grumpkin_elements>(
-        st, static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
-        static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript), d, columns);
-  }
+  });
 }
 
 u64 sumcheck_transcript_columns_workspace_bytes(unsigned field_id, const sumcheck_inputs& d) {
   check_sumcheck_limits(d);
-  BZ_RELEASE_ASSERT(field_id <= 1, "unsupported field id");
-  return field_id == 0 ? columns_workspace_layout<scalar25_field>{d}.total
-                       : columns_workspace_layout<grumpkin_fq29>{d}.total;
+  return with_elements(field_id, [&](auto elements) -> u64 {
+    return chain_layout<typename decltype(elements)::F>{d, true}.total;
+  });
 }
 
 void prove_sumcheck_transcript_device_columns(void* polynomials, void* evaluation_point,
@@ -790,35 +698,24 @@ void prove_sumcheck_transcript_device_columns(void* polynomials, void* evaluatio
                                               u64 workspace_bytes, hipStream_t stream) {
   check_sumcheck_limits(d);
   check_column_lengths(d, columns);
-  if (field_id == 0) {
-    prove_device_columns<scalar25519_elements>(
-        static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
-        static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript), d, columns, workspace,
-        workspace_bytes, stream);
-  } else if (field_id == 1) {
-    prove_device_columns<grumpkin_elements>(
-        static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
-        static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript), d, columns, workspace,
-        workspace_bytes, stream);
-  } else {
-    BZ_RELEASE_ASSERT(false, "unsupported field id");
-  }
+  with_elements(field_id, [&](auto elements) {
+    prove_device_columns<decltype(elements)>(
+        chain_target{static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
+                     static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript), workspace,
+                     workspace_bytes, stream},
+        d, columns);
+  });
 }
 
 bool verify_sumcheck(void* expected_sum, void* evaluation_point, void* transcript, unsigned field_id,
                      const void* round_polynomials, unsigned num_variables, unsigned round_degree) {
   BZ_RELEASE_ASSERT(num_variables > 0 && round_degree > 0,
                     "sumcheck verification needs num_variables > 0 and round_degree > 0");
-  auto* t = static_cast<transcript_state*>(transcript);
-  if (field_id == 0) {
-    return verify<scalar25519_elements>(static_cast<u8*>(expected_sum),
-                                        static_cast<u8*>(evaluation_point), t,
-                                        static_cast<const u8*>(round_polynomials), num_variables,
-                                        round_degree);
-  }
-  BZ_RELEASE_ASSERT(field_id == 1, "unsupported field id");
-  return verify<grumpkin_elements>(static_cast<u8*>(expected_sum), static_cast<u8*>(evaluation_point),
-                                   t, static_cast<const u8*>(round_polynomials), num_variables,
-                                   round_degree);
+  return with_elements(field_id, [&](auto elements) {
+    return verify<decltype(elements)>(
+        static_cast<u8*>(expected_sum), static_cast<u8*>(evaluation_point),
+        static_cast<transcript_state*>(transcript), static_cast<const u8*>(round_polynomials),
+        num_variables, round_degree);
+  });
 }
 } // namespace bz::proof
