@@ -213,6 +213,15 @@ def load():
         lib.bzamd_prove_sumcheck_transcript_device_columns.argtypes = [vp, vp, vp, vp, cu, vp, vp,
                                                                        u64, vp]
         lib.bzamd_prove_sumcheck_transcript_device_columns.restype = None
+    if hasattr(lib, "bzamd_combine_columns_device"):
+        lib.bzamd_mle_evaluation_vector.argtypes = [vp, cu, vp, cu, u64]
+        lib.bzamd_mle_evaluation_vector.restype = None
+        lib.bzamd_mle_evaluation_vector_device.argtypes = [vp, cu, vp, cu, u64, vp]
+        lib.bzamd_mle_evaluation_vector_device.restype = None
+        lib.bzamd_combine_columns.argtypes = [vp, vp, cu, vp]
+        lib.bzamd_combine_columns.restype = None
+        lib.bzamd_combine_columns_device.argtypes = [vp, vp, cu, vp, vp]
+        lib.bzamd_combine_columns_device.restype = None
     _lib = lib
     return lib
 
@@ -708,6 +717,69 @@ def prove_sumcheck_transcript_device_columns(field_id, descriptors, product_tabl
         None if transcript_ptr is None else int(transcript_ptr), field_id, ctypes.byref(c),
         int(workspace_ptr), workspace_bytes,
         None if stream is None else ctypes.c_void_p(int(stream)))
+
+
+class bzamd_column_combination(ctypes.Structure):
+    _fields_ = [("columns", ctypes.POINTER(sxt_sequence_descriptor)),
+                ("coefficients", ctypes.c_void_p), ("evaluations", ctypes.c_void_p),
+                ("num_columns", ctypes.c_uint), ("n", ctypes.c_uint64)]
+
+
+def mle_evaluation_vector(field_id, evaluation_point, n, num_variables=None):
+    """bzamd_mle_evaluation_vector (host operands, either backend).  evaluation_point: uint8
+    [num_variables, 32] (num_variables defaults to its rows) -> uint8 [n, 32]:
+    vector[i] = prod_t (bit_{v-1-t}(i) ? r_t : 1 - r_t)"""
+    point = np.ascontiguousarray(evaluation_point, dtype=np.uint8)
+    if num_variables is None:
+        num_variables = point.size // 32
+    vector = np.zeros((max(int(n), 1), 32), dtype=np.uint8)
+    load().bzamd_mle_evaluation_vector(_ptr(vector), field_id, _ptr(point), num_variables, n)
+    return vector[:n]
+
+
+def mle_evaluation_vector_device(field_id, vector_ptr, evaluation_point_ptr, num_variables, n,
+                                 stream=None):
+    """bzamd_mle_evaluation_vector_device: enqueue only.  Both pointers are memory of the current
+    device as integers (None: a null pointer); `stream` a hipStream_t as an integer (None: the
+    default stream)."""
+    load().bzamd_mle_evaluation_vector_device(
+        None if vector_ptr is None else int(vector_ptr), field_id,
+        None if evaluation_point_ptr is None else int(evaluation_point_ptr), num_variables, n,
+        None if stream is None else ctypes.c_void_p(int(stream)))
+
+
+def combine_columns(field_id, columns, coefficients, n, evaluations=None, product=None):
+    """bzamd_combine_columns (host operands, either backend).  columns: as prove_sumcheck_columns;
+    coefficients, evaluations: uint8 [num_columns, 32]; product: a uint8 [32] buffer the call may
+    write (None: a null pointer) -> (combined uint8 [n, 32], product)"""
+    descs, keep = make_descriptors(_column_pairs(columns))
+    coefficients = np.ascontiguousarray(coefficients, dtype=np.uint8)
+    if evaluations is not None:
+        evaluations = np.ascontiguousarray(evaluations, dtype=np.uint8)
+    combined = np.zeros((max(int(n), 1), 32), dtype=np.uint8)
+    c = bzamd_column_combination(descs, coefficients.ctypes.data,
+                                 None if evaluations is None else evaluations.ctypes.data,
+                                 len(keep), n)
+    load().bzamd_combine_columns(_ptr(combined), _ptr(product), field_id, ctypes.byref(c))
+    return combined[:n], product
+
+
+def combine_columns_device(field_id, descriptors, coefficients_ptr, n, combined_ptr,
+                           evaluations_ptr=None, product_ptr=None, stream=None):
+    """bzamd_combine_columns_device: enqueue only.  descriptors: one (device_ptr, n_j, nbytes,
+    signed) per column, or a ready sxt_sequence_descriptor array (the one the MSM took); every
+    *_ptr is memory of the current device as an integer; `stream` a hipStream_t as an integer
+    (None: the default stream)."""
+    if isinstance(descriptors, ctypes.Array):
+        descs, num_columns = descriptors, len(descriptors)
+    else:
+        descs, num_columns = _device_descriptors(descriptors)
+    c = bzamd_column_combination(descs, int(coefficients_ptr),
+                                 None if evaluations_ptr is None else int(evaluations_ptr),
+                                 num_columns, n)
+    load().bzamd_combine_columns_device(
+        int(combined_ptr), None if product_ptr is None else int(product_ptr), field_id,
+        ctypes.byref(c), None if stream is None else ctypes.c_void_p(int(stream)))
 
 
 class MultiexpHandle:

@@ -35,6 +35,7 @@ SOURCES = [
     "proof/sumcheck.hip",
     "proof/sumcheck_columns.hip",
     "proof/sumcheck_transcript.hip",
+    "proof/mle_opening.hip",
     "api/capi.hip",
 ]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-I" + ROOT,

@@ -24,6 +24,7 @@
 #include "blitzar_amd/csrc/fixed/dump.h"
 #include "blitzar_amd/csrc/fixed/handle.h"
 #include "blitzar_amd/csrc/proof/inner_product.h"
+#include "blitzar_amd/csrc/proof/mle_opening.h"
 #include "blitzar_amd/csrc/proof/sumcheck.h"
 #include "blitzar_amd/csrc/proof/sumcheck_transcript.h"
 #include "blitzar_amd/csrc/proof/transcript.h"
@@ -1729,12 +1730,12 @@ void bzamd_prove_sumcheck_device(void* polynomials, void* evaluation_point, void
 namespace {
 // the MLEs of a bzamd_sumcheck_columns, checked by the rule of the MSM entry points
 // (check_descriptors), so one array serves both
-std::vector<proof::sumcheck_column> checked_sumcheck_columns(
-    const struct bzamd_sumcheck_columns* columns) {
-  BZ_RELEASE_ASSERT(columns->num_mles == 0 || columns->mles != nullptr, "descriptors is null");
-  std::vector<proof::sumcheck_column> cols(columns->num_mles);
-  for (u32 j = 0; j < columns->num_mles; ++j) {
-    const sxt_sequence_descriptor& d = columns->mles[j];
+extern "C++" std::vector<proof::sumcheck_column> checked_sumcheck_columns(
+    const struct sxt_sequence_descriptor* descriptors, u32 count) {
+  BZ_RELEASE_ASSERT(count == 0 || descriptors != nullptr, "descriptors is null");
+  std::vector<proof::sumcheck_column> cols(count);
+  for (u32 j = 0; j < count; ++j) {
+    const sxt_sequence_descriptor& d = descriptors[j];
     BZ_RELEASE_ASSERT(d.n == 0 || d.data != nullptr, "descriptor has n > 0 but null data");
     BZ_RELEASE_ASSERT(d.element_nbytes != 0 && d.element_nbytes <= 32,
                       "element_nbytes must be in [1, 32]");
@@ -1743,6 +1744,10 @@ std::vector<proof::sumcheck_column> checked_sumcheck_columns(
     cols[j] = proof::sumcheck_column{d.data, d.n, d.element_nbytes, d.is_signed != 0};
   }
   return cols;
+}
+extern "C++" std::vector<proof::sumcheck_column> checked_sumcheck_columns(
+    const struct bzamd_sumcheck_columns* columns) {
+  return checked_sumcheck_columns(columns->mles, columns->num_mles);
 }
 
 // bzamd_prove_sumcheck_columns / _device_columns
@@ -1913,6 +1918,55 @@ int bzamd_verify_sumcheck(void* expected_sum, void* evaluation_point,
                                 round_polynomials, num_variables, round_degree)
              ? 1
              : 0;
+}
+
+// from the sumcheck's outputs to the inner-product prover's inputs (proof/mle_opening.hip)
+void bzamd_mle_evaluation_vector(void* vector, unsigned field_id, const void* evaluation_point,
+                                 unsigned num_variables, uint64_t n) {
+  check_arguments("bzamd_mle_evaluation_vector", vector != nullptr && evaluation_point != nullptr);
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::mle_evaluation_vector(st, vector, field_id, evaluation_point, num_variables, n);
+}
+
+void bzamd_mle_evaluation_vector_device(void* vector, unsigned field_id,
+                                        const void* evaluation_point, unsigned num_variables,
+                                        uint64_t n, void* stream) {
+  check_arguments("bzamd_mle_evaluation_vector_device",
+                  vector != nullptr && evaluation_point != nullptr);
+  proof::mle_evaluation_vector_device(vector, field_id, evaluation_point, num_variables, n,
+                                      device_form(stream).stream);
+}
+
+namespace {
+// the combination's columns, checked as in prove_sumcheck_columns_entry
+extern "C++" std::vector<proof::sumcheck_column> combination_form_columns(
+    const char* name, const void* combined, const struct bzamd_column_combination* c) {
+  check_arguments(name, combined != nullptr && c != nullptr);
+  BZ_RELEASE_ASSERT(c->coefficients != nullptr, "coefficients is null");
+  return checked_sumcheck_columns(c->columns, c->num_columns);
+}
+proof::column_combination combination_of(const struct bzamd_column_combination& c,
+                                         const std::vector<proof::sumcheck_column>& cols) {
+  return {cols.data(), c.coefficients, c.evaluations, c.num_columns, c.n};
+}
+} // namespace
+
+void bzamd_combine_columns(void* combined, void* product, unsigned field_id,
+                           const struct bzamd_column_combination* c) {
+  const std::vector<proof::sumcheck_column> cols =
+      combination_form_columns("bzamd_combine_columns", combined, c);
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::combine_columns(st, combined, product, field_id, combination_of(*c, cols));
+}
+
+void bzamd_combine_columns_device(void* combined, void* product, unsigned field_id,
+                                  const struct bzamd_column_combination* c, void* stream) {
+  const std::vector<proof::sumcheck_column> cols =
+      combination_form_columns("bzamd_combine_columns_device", combined, c);
+  proof::combine_columns_device(combined, product, field_id, combination_of(*c, cols),
+                                device_form(stream).stream);
 }
 
 //--------------------------------------------------------------------------------------------------

@@ -1,0 +1,395 @@
+// From the sumcheck's outputs to the inner-product prover's inputs (bzamd_mle_evaluation_vector*,
+// bzamd_combine_columns*), both exact and both enqueue-only in their device forms.
+//
+// The evaluation vector.  vector[i] = prod_t (bit_{v-1-t}(i) ? r_t : 1 - r_t): bit b of the row
+// index belongs to r_{v-1-b}, the bit order of the prover's fold (round 0 binds the top bit).  One
+// product per challenge and row would be v Montgomery products per 32-byte store.  Instead the
+// index is split into three bit fields,
+//   low  = bits [0, lb)          lb = min(v, kLowBits)
+//   mid  = bits [lb, lb + mb)    mb = min(v - lb, kMidBits)
+//   high = bits [lb + mb, v)
+// and a workgroup holds in LDS the table of the low field (2^lb elements) and of the mid field
+// (2^mb), each built by doubling: the table over one bit more is [T (1 - r), T r], and T (1 - r) =
+// T - T r, so a table of 2^k entries costs 2^k - 1 products.  A tile is the 2^(lb + mb) consecutive
+// rows that share their high field; workgroups walk tiles grid-stride.  Per tile 2^mb lanes make
+// pm[m] = mid[m] * (the high field's factors), hb products each, and a row is then the ONE product
+// pm[mid(i)] * low[low(i)] plus the product inside E::store that leaves the engine's Montgomery
+// form.  With lb = mb = 5 (tiles of 1024 rows, four rows per lane) that is per output element
+//   1 + 32 hb / 1024 + 1 (store)  =  2.19 at v = 16,  2.31 at v = 20,  2.63 at v = 30
+// plus the workgroup's tables and challenges (62 + v products) over the rows it writes (at least
+// one tile: < 0.1).  No array is indexed at run time outside LDS: no scratch memory.  LDS: the two
+// tables, pm and the challenges, (3 * 32 + 30) * 36 = 4536 bytes, which does not bound occupancy;
+// larger fields (6 + 6) would save 0.1 products per element and leave 16 tiles, so 16 workgroups,
+// at n = 2^16.
+//
+// The combination.  One row per lane; a row of column j is fetched as the raw residue of its bytes
+// (load_raw, proof/sumcheck_columns.h), and the coefficient carries the conversion constant of the
+// column's kind, multiplied in once per workgroup while the coefficients go to LDS: a row costs one
+// product and one lazy addition per column (normalised and reduced every fourth).  The views
+// travel as kernel arguments, kCombineChunk at a time; a call with more columns launches the kernel
+// once per chunk and the later launches add to what `combined` holds, which is exact.  So the call
+// needs no memory beside its operands, however many columns it takes.
+#include "blitzar_amd/csrc/proof/mle_opening.h"
+
+#include <cstring>
+#include <vector>
+
+#include "blitzar_amd/csrc/proof/sumcheck_columns.h"
+
+namespace bz::proof {
+namespace {
+constexpr u32 kLowBits = 5, kMidBits = 5;
+constexpr u32 kVectorThreads = 256;
+constexpr u32 kVectorBlocks = 2048; // 8 workgroups per CU: one wave per SIMD and workgroup, 2 deep
+constexpr u32 kMaxVariables = 30;
+
+constexpr u32 kCombineChunk = 32; // views per launch: 1 KiB of kernel arguments
+constexpr u32 kCombineThreads = 256;
+constexpr u32 kCombineBlocks = 4096;
+
+struct vector_split {
+  u32 lb, mb, hb;
+};
+BZ_HD vector_split split_of(u32 num_variables) {
+  const u32 lb = num_variables < kLowBits ? num_variables : kLowBits;
+  const u32 mb = num_variables - lb < kMidBits ? num_variables - lb : kMidBits;
+  return {lb, mb, num_variables - lb - mb};
+}
+
+//--------------------------------------------------------------------------------------------------
+// device kernels
+//--------------------------------------------------------------------------------------------------
+template <class E>
+__global__ void __launch_bounds__(kVectorThreads)
+    k_mle_evaluation_vector(u64* __restrict__ vector, const u8* __restrict__ point,
+                            u32 num_variables, u64 n) {
+  using F = typename E::F;
+  using fe = typename F::fe;
+  __shared__ fe rs[kMaxVariables];      // r_t, engine form
+  __shared__ fe tables[2][1u << kLowBits]; // [0]: the low field's, [1]: the mid field's
+  __shared__ fe pm[1u << kMidBits];     // the tile's high-field product times the mid table
+  const vector_split s = split_of(num_variables);
+  const u32 t = threadIdx.x;
+  if (t < num_variables) rs[t] = E::load(point + 32 * t);
+  if (t == 0 || t == 32) tables[t >> 5][0] = F::one();
+  __syncthreads();
+  // both tables by doubling, lanes 0 .. 31 the low one and 32 .. 63 the mid one: step b appends bit
+  // b of the field, whose challenge is r_{v-1-b} (low) or r_{v-1-lb-b} (mid)
+  for (u32 b = 0; b < s.lb; ++b) {
+    const u32 which = t >> 5, k = t & 31;
+    if (t < 64 && k < (1u << b) && b < (which == 0 ? s.lb : s.mb)) {
+      const fe r = rs[num_variables - 1 - (which == 0 ? 0 : s.lb) - b];
+      const fe low = tables[which][k];
+      const fe high = F::mul(low, r);
+      tables[which][k + (1u << b)] = high;
+      tables[which][k] = fsub<F>(low, high);
+    }
+    __syncthreads();
+  }
+  const u32 tile_bits = s.lb + s.mb;
+  const u64 tile_rows = u64{1} << tile_bits;
+  const u64 num_tiles = (n + tile_rows - 1) >> tile_bits;
+  for (u64 h = blockIdx.x; h < num_tiles; h += gridDim.x) {
+    if (t < (1u << s.mb)) {
+      // bit b of h is bit lb + mb + b of the row: r_{hb-1-b}
+      fe p = tables[1][t];
+      for (u32 b = 0; b < s.hb; ++b) {
+        const fe r = rs[s.hb - 1 - b];
+        p = F::mul(p, ((h >> b) & 1) != 0 ? r : fsub<F>(F::one(), r));
+      }
+      pm[t] = p;
+    }
+    __syncthreads();
+    for (u64 x = t; x < tile_rows; x += kVectorThreads) {
+      const u64 i = (h << tile_bits) + x;
+      if (i < n) {
+        const fe value = F::mul(pm[x >> s.lb], tables[0][x & ((1u << s.lb) - 1)]);
+        u64 w[4];
+        E::store_words(w, value);
+        u64* out = vector + 4 * i;
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) out[k] = w[k];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+struct combine_views {
+  column_view v[kCombineChunk];
+};
+
+// combined[i] (+)= sum_{j < count} coefficients[j] views.v[j][i], i < n; `add`: to what combined holds
+template <class E>
+__global__ void __launch_bounds__(kCombineThreads)
+    k_combine_columns(u64* combined, const combine_views views, const u8* __restrict__ coefficients,
+                      u32 count, u64 n, u32 add) {
+  using F = typename E::F;
+  using fe = typename F::fe;
+  __shared__ fe scaled[kCombineChunk];
+  if (threadIdx.x < count) {
+    scaled[threadIdx.x] = F::mul(E::load(coefficients + 32 * threadIdx.x),
+                                 E::conversion(views.v[threadIdx.x].nbytes == E::element_bytes));
+  }
+  __syncthreads();
+  for (u64 i = static_cast<u64>(blockIdx.x) * kCombineThreads + threadIdx.x; i < n;
+       i += static_cast<u64>(gridDim.x) * kCombineThreads) {
+    u64* out = combined + 4 * i;
+    fe acc = F::zero();
+    if (add != 0) {
+      u64 w[4];
+#pragma unroll
+      for (u32 k = 0; k < 4; ++k) w[k] = out[k];
+      acc = E::load(reinterpret_cast<const u8*>(w));
+    }
+    for (u32 j = 0; j < count; ++j) {
+      const column_view c = views.v[j];
+      // lazy: limbs and value grow by one product's a column, swept and reduced every fourth
+      if (i < c.n) acc = F::add(acc, F::mul(load_raw<F>(c, i), scaled[j]));
+      if ((j & 3) == 3) acc = F::reduce(F::norm(acc));
+    }
+    acc = F::reduce(F::norm(acc));
+    u64 w[4];
+    E::store_words(w, acc);
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) out[k] = w[k];
+  }
+}
+
+// product = sum_j coefficients[j] evaluations[j]: one wavefront
+template <class E>
+__global__ void __launch_bounds__(64)
+    k_combine_product(u8* __restrict__ product, const u8* __restrict__ coefficients,
+                      const u8* __restrict__ evaluations, u32 count) {
+  using F = typename E::F;
+  using fe = typename F::fe;
+  __shared__ fe tree[64];
+  fe sum = F::zero();
+  for (u32 j = threadIdx.x; j < count; j += 64) {
+    sum = fadd<F>(sum, F::mul(E::load(coefficients + 32 * j), E::load(evaluations + 32 * j)));
+  }
+  tree[threadIdx.x] = sum;
+  __syncthreads();
+  for (u32 stride = 32; stride > 0; stride >>= 1) {
+    if (threadIdx.x < stride) {
+      tree[threadIdx.x] = fadd<F>(tree[threadIdx.x], tree[threadIdx.x + stride]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) E::store(product, tree[0]);
+}
+
+//--------------------------------------------------------------------------------------------------
+// checks
+//--------------------------------------------------------------------------------------------------
+void check_vector_arguments(const void* vector, const void* point, unsigned num_variables, u64 n) {
+  BZ_RELEASE_ASSERT(vector != nullptr && point != nullptr,
+                    "null argument to the MLE evaluation vector");
+  BZ_RELEASE_ASSERT(num_variables >= 1 && num_variables <= kMaxVariables,
+                    "the MLE evaluation vector needs 1 <= num_variables <= 30");
+  BZ_RELEASE_ASSERT(n >= 1 && n <= (u64{1} << num_variables),
+                    "the MLE evaluation vector needs 1 <= n <= 2^num_variables");
+  BZ_RELEASE_ASSERT(reinterpret_cast<uintptr_t>(vector) % 8 == 0,
+                    "the MLE evaluation vector must be 8-byte aligned");
+}
+
+void check_combination(const void* combined, const column_combination& c) {
+  BZ_RELEASE_ASSERT(c.num_columns >= 1, "the column combination needs at least one column");
+  BZ_RELEASE_ASSERT(combined != nullptr && c.columns != nullptr && c.coefficients != nullptr,
+                    "null argument to the column combination");
+  BZ_RELEASE_ASSERT(c.n >= 1 && c.n <= (u64{1} << 30), "the column combination needs 1 <= n <= 2^30");
+  BZ_RELEASE_ASSERT(reinterpret_cast<uintptr_t>(combined) % 8 == 0,
+                    "the combined vector must be 8-byte aligned");
+  for (u32 j = 0; j < c.num_columns; ++j) {
+    BZ_RELEASE_ASSERT(c.columns[j].n <= c.n, "a combined column is longer than n");
+  }
+}
+
+//--------------------------------------------------------------------------------------------------
+// host backend: plain loops over the same element arithmetic
+//--------------------------------------------------------------------------------------------------
+template <class E>
+void evaluation_vector_host(u64* vector, const u8* point, u32 num_variables, u64 n) {
+  using F = typename E::F;
+  using fe = typename F::fe;
+  fe r[kMaxVariables], one_minus_r[kMaxVariables];
+  for (u32 t = 0; t < num_variables; ++t) {
+    r[t] = E::load(point + 32 * t);
+    one_minus_r[t] = fsub<F>(F::one(), r[t]);
+  }
+  for (u64 i = 0; i < n; ++i) {
+    fe p = F::one();
+    for (u32 t = 0; t < num_variables; ++t) {
+      p = F::mul(p, ((i >> (num_variables - 1 - t)) & 1) != 0 ? r[t] : one_minus_r[t]);
+    }
+    E::store_words(vector + 4 * i, p);
+  }
+}
+
+template <class E> void combine_host(u64* combined, u8* product, const column_combination& c) {
+  using F = typename E::F;
+  using fe = typename F::fe;
+  const u8* coefficients = static_cast<const u8*>(c.coefficients);
+  std::vector<column_view> views(c.num_columns);
+  std::vector<fe> scaled(c.num_columns);
+  for (u32 j = 0; j < c.num_columns; ++j) {
+    views[j] = make_column_view(c.columns[j]);
+    scaled[j] = F::mul(E::load(coefficients + 32 * j),
+                       E::conversion(views[j].nbytes == E::element_bytes));
+  }
+  for (u64 i = 0; i < c.n; ++i) {
+    fe acc = F::zero();
+    for (u32 j = 0; j < c.num_columns; ++j) {
+      if (i < views[j].n) acc = fadd<F>(acc, F::mul(load_raw<F>(views[j], i), scaled[j]));
+    }
+    E::store_words(combined + 4 * i, acc);
+  }
+  if (product != nullptr && c.evaluations != nullptr) {
+    const u8* evaluations = static_cast<const u8*>(c.evaluations);
+    fe sum = F::zero();
+    for (u32 j = 0; j < c.num_columns; ++j) {
+      sum = fadd<F>(sum, F::mul(E::load(coefficients + 32 * j), E::load(evaluations + 32 * j)));
+    }
+    E::store(product, sum);
+  }
+}
+
+//--------------------------------------------------------------------------------------------------
+// device forms: enqueue only
+//--------------------------------------------------------------------------------------------------
+template <class E>
+void evaluation_vector_enqueue(u64* vector, const u8* point, u32 num_variables, u64 n,
+                               hipStream_t stream) {
+  const vector_split s = split_of(num_variables);
+  const u64 tile_rows = u64{1} << (s.lb + s.mb);
+  const u64 num_tiles = (n + tile_rows - 1) / tile_rows;
+  const u32 blocks = static_cast<u32>(std::min<u64>(kVectorBlocks, num_tiles));
+  hipLaunchKernelGGL((k_mle_evaluation_vector<E>), dim3(blocks), dim3(kVectorThreads), 0, stream,
+                     vector, point, num_variables, n);
+  BZ_HIP_CHECK(hipGetLastError());
+  g_kernel_launches += 1;
+}
+
+template <class E>
+void combine_enqueue(u64* combined, u8* product, const column_combination& c, hipStream_t stream) {
+  const u8* coefficients = static_cast<const u8*>(c.coefficients);
+  const u32 blocks = static_cast<u32>(
+      std::min<u64>(kCombineBlocks, (c.n + kCombineThreads - 1) / kCombineThreads));
+  for (u32 first = 0; first < c.num_columns; first += kCombineChunk) {
+    const u32 count = std::min(kCombineChunk, c.num_columns - first);
+    combine_views views;
+    std::memset(&views, 0, sizeof(views));
+    for (u32 j = 0; j < count; ++j) views.v[j] = make_column_view(c.columns[first + j]);
+    hipLaunchKernelGGL((k_combine_columns<E>), dim3(blocks), dim3(kCombineThreads), 0, stream,
+                       combined, views, coefficients + static_cast<size_t>(32) * first, count, c.n,
+                       first != 0 ? 1u : 0u);
+    BZ_HIP_CHECK(hipGetLastError());
+    g_kernel_launches += 1;
+  }
+  if (product != nullptr && c.evaluations != nullptr) {
+    hipLaunchKernelGGL((k_combine_product<E>), dim3(1), dim3(64), 0, stream, product, coefficients,
+                       static_cast<const u8*>(c.evaluations), c.num_columns);
+    BZ_HIP_CHECK(hipGetLastError());
+    g_kernel_launches += 1;
+  }
+}
+} // namespace
+
+void mle_evaluation_vector_device(void* vector, unsigned field_id, const void* evaluation_point,
+                                  unsigned num_variables, u64 n, hipStream_t stream) {
+  check_vector_arguments(vector, evaluation_point, num_variables, n);
+  with_elements(field_id, [&](auto elements) {
+    evaluation_vector_enqueue<decltype(elements)>(static_cast<u64*>(vector),
+                                                  static_cast<const u8*>(evaluation_point),
+                                                  num_variables, n, stream);
+  });
+}
+
+void mle_evaluation_vector(api_state& st, void* vector, unsigned field_id,
+                           const void* evaluation_point, unsigned num_variables, u64 n) {
+  check_vector_arguments(vector, evaluation_point, num_variables, n);
+  with_elements(field_id, [&](auto elements) {
+    using E = decltype(elements);
+    if (st.backend != 2) {
+      evaluation_vector_host<E>(static_cast<u64*>(vector), static_cast<const u8*>(evaluation_point),
+                                num_variables, n);
+      return;
+    }
+    // the point up, the device form, the vector down: memory of the call's own
+    hipStream_t stream = st.primary().stream;
+    BZ_HIP_CHECK(hipSetDevice(st.primary().device));
+    const size_t point_bytes = static_cast<size_t>(32) * num_variables;
+    const size_t vector_bytes = static_cast<size_t>(32) * n;
+    device_arena own;
+    own.reset(device_arena::padded(point_bytes) + device_arena::padded(vector_bytes), stream);
+    u8* d_point = own.take<u8>(point_bytes);
+    u64* d_vector = own.take<u64>(4 * n);
+    BZ_HIP_CHECK(hipMemcpyAsync(d_point, evaluation_point, point_bytes, hipMemcpyHostToDevice, stream));
+    evaluation_vector_enqueue<E>(d_vector, d_point, num_variables, n, stream);
+    BZ_HIP_CHECK(hipMemcpyAsync(vector, d_vector, vector_bytes, hipMemcpyDeviceToHost, stream));
+    BZ_HIP_CHECK(hipStreamSynchronize(stream));
+    own.release();
+  });
+}
+
+void combine_columns_device(void* combined, void* product, unsigned field_id,
+                            const column_combination& c, hipStream_t stream) {
+  check_combination(combined, c);
+  with_elements(field_id, [&](auto elements) {
+    combine_enqueue<decltype(elements)>(static_cast<u64*>(combined), static_cast<u8*>(product), c,
+                                        stream);
+  });
+}
+
+void combine_columns(api_state& st, void* combined, void* product, unsigned field_id,
+                     const column_combination& c) {
+  check_combination(combined, c);
+  with_elements(field_id, [&](auto elements) {
+    using E = decltype(elements);
+    if (st.backend != 2) {
+      combine_host<E>(static_cast<u64*>(combined), static_cast<u8*>(product), c);
+      return;
+    }
+    // the columns up at their own width, the device form, the results down
+    hipStream_t stream = st.primary().stream;
+    BZ_HIP_CHECK(hipSetDevice(st.primary().device));
+    const bool with_product = product != nullptr && c.evaluations != nullptr;
+    const size_t element_bytes = static_cast<size_t>(32) * c.num_columns;
+    const size_t combined_bytes = static_cast<size_t>(32) * c.n;
+    size_t bytes = device_arena::padded(combined_bytes) + 2 * device_arena::padded(element_bytes) + 256;
+    for (u32 j = 0; j < c.num_columns; ++j) {
+      bytes += device_arena::padded(c.columns[j].n * c.columns[j].nbytes);
+    }
+    device_arena own;
+    own.reset(bytes, stream);
+    u64* d_combined = own.take<u64>(4 * c.n);
+    u8* d_coefficients = own.take<u8>(element_bytes);
+    u8* d_evaluations = own.take<u8>(element_bytes);
+    u8* d_product = own.take<u8>(32);
+    BZ_HIP_CHECK(hipMemcpyAsync(d_coefficients, c.coefficients, element_bytes, hipMemcpyHostToDevice,
+                                stream));
+    if (with_product) {
+      BZ_HIP_CHECK(hipMemcpyAsync(d_evaluations, c.evaluations, element_bytes, hipMemcpyHostToDevice,
+                                  stream));
+    }
+    std::vector<sumcheck_column> on_device(c.columns, c.columns + c.num_columns);
+    for (sumcheck_column& column : on_device) {
+      const size_t column_bytes = column.n * column.nbytes;
+      u8* staged = own.take<u8>(column_bytes);
+      if (column_bytes != 0) {
+        BZ_HIP_CHECK(hipMemcpyAsync(staged, column.data, column_bytes, hipMemcpyHostToDevice, stream));
+      }
+      column.data = staged;
+    }
+    const column_combination staged{on_device.data(), d_coefficients,
+                                    with_product ? d_evaluations : nullptr, c.num_columns, c.n};
+    combine_enqueue<E>(d_combined, with_product ? d_product : nullptr, staged, stream);
+    BZ_HIP_CHECK(hipMemcpyAsync(combined, d_combined, combined_bytes, hipMemcpyDeviceToHost, stream));
+    if (with_product) {
+      BZ_HIP_CHECK(hipMemcpyAsync(product, d_product, 32, hipMemcpyDeviceToHost, stream));
+    }
+    BZ_HIP_CHECK(hipStreamSynchronize(stream));
+    own.release();
+  });
+}
+} // namespace bz::proof

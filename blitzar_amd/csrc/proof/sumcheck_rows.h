@@ -29,6 +29,8 @@ struct scalar25519_elements {
   static constexpr u32 element_bytes = 32, product_stride = 36;
   BZ_HD static F::fe load(const u8* p) { return s25::to_mont(s25::load(p)); }
   BZ_HD static void store(u8* p, const F::fe& v) { s25::store(p, s25::from_mont(v)); }
+  // the same bytes as little-endian words (for destinations known to be 8-byte aligned)
+  BZ_HD static void store_words(u64* w, const F::fe& v) { s25::store_words(w, s25::from_mont(v)); }
   // engine form of little-endian words: of an element's 32 bytes (`element`: what load() makes of
   // those bytes) or of an integer below 2^248, as raw * conversion(element) / R
   BZ_HD static F::fe conversion(bool element) {
@@ -52,6 +54,7 @@ struct grumpkin_elements {
     F::to_mont64(w, v);
     std::memcpy(p, w, 32);
   }
+  BZ_HD static void store_words(u64* w, const F::fe& v) { F::to_mont64(w, v); }
   // an element is x 2^256 and takes from_mont64's constant; an integer x becomes x R^2 / R with the
   // engine's R = 2^261: the caller's Montgomery form is never made
   BZ_HD static F::fe conversion(bool element) {

@@ -465,6 +465,60 @@ void bzamd_verify_inner_product_device(void* verdict, void* transcript, uint64_t
                                        const void* r_vector, const void* ap_value,
                                        void* workspace, uint64_t workspace_bytes, void* stream);
 
+/* From the sumcheck's outputs to the inner-product argument's inputs: the two vectors with which
+ * one inner-product proof opens every claimed evaluation mle_evaluations[j] = f_j(r).  Both are
+ * exact field arithmetic; elements are 32 bytes in the representation sxt_prove_sumcheck takes for
+ * the field (field_id 0 or 1; anything else aborts) and are written canonical.
+ *
+ * The evaluation vector of a point: with v = num_variables and r_0 .. r_{v-1} = evaluation_point,
+ *   vector[i] = prod_{t < v} (bit_{v-1-t}(i) ? r_t : 1 - r_t),   i < n,
+ * the bit order of the fold above bzamd_prove_sumcheck (round 0 binds the top bit), so that
+ * sum_i T_0[j][i] vector[i] = T_v[j][0] = mle_evaluations[j] exactly; n = 1, v = 1 gives 1 - r_0.
+ * 1 <= num_variables <= 30 and 1 <= n <= 2^num_variables (num_variables may exceed ceil_log2(n));
+ * `vector` must be 8-byte aligned; null pointers abort. */
+/* HOST operands, blocking, cpu and gpu backends (the gpu backend uploads the point, runs the device
+ * form and downloads the vector) */
+void bzamd_mle_evaluation_vector(void* vector, unsigned field_id, const void* evaluation_point,
+                                 unsigned num_variables, uint64_t n);
+/* DEVICE pointers on the current HIP device: vector (n x 32 bytes) and evaluation_point
+ * (num_variables x 32 bytes, read in stream order: the call may follow the sumcheck chain that
+ * writes it with no synchronise in between).  gpu backend only.  The call only enqueues on
+ * `stream`: no synchronise, no allocation, no callback, no workspace. */
+void bzamd_mle_evaluation_vector_device(void* vector, unsigned field_id,
+                                        const void* evaluation_point, unsigned num_variables,
+                                        uint64_t n, void* stream);
+
+/* A linear combination of typed columns, widened to scalars:
+ *   combined[i] = sum_j coefficients[j] * column_j[i],   i < n,
+ * n x 32 bytes.  The columns are the MSM's / sumcheck's descriptors and mean what they mean in
+ * bzamd_prove_sumcheck_columns: columns[j].n <= n rows (longer aborts), rows past a column's end
+ * are zero (n = 0 with data = NULL is a zero column); element_nbytes 1 .. 31 little-endian
+ * integers, two's complement when is_signed; element_nbytes 32 the field's elements, unreduced
+ * values included; validated by the same rule.  When `product` and `evaluations` are both
+ * non-NULL, product = sum_j coefficients[j] * evaluations[j] (32 bytes): the inner product the
+ * proof claims when evaluations are the sumcheck's mle_evaluations.  When either is NULL nothing
+ * is written there.  1 <= n <= 2^30, 1 <= num_columns (no upper limit); `combined` must be 8-byte
+ * aligned and must not overlap a column. */
+struct bzamd_column_combination {
+  const struct sxt_sequence_descriptor* columns; /* num_columns descriptors */
+  const void* coefficients;                      /* num_columns x 32 bytes */
+  const void* evaluations;                       /* may be NULL: num_columns x 32 bytes */
+  unsigned num_columns;
+  uint64_t n;
+};
+/* HOST operands (columns[j].data included), blocking, cpu and gpu backends.  The gpu backend
+ * uploads the columns at their own width, runs the device form and synchronises once. */
+void bzamd_combine_columns(void* combined, void* product, unsigned field_id,
+                           const struct bzamd_column_combination* c);
+/* DEVICE pointers on the current HIP device: combined, product (may be NULL), coefficients,
+ * evaluations (may be NULL) and every columns[j].data (any address; read in stream order, never
+ * written).  HOST: the struct and the descriptors, which are read before the call returns.  gpu
+ * backend only.  The call only enqueues on `stream`: no synchronise, no allocation, no callback,
+ * no workspace (the descriptors travel as kernel arguments, 32 columns to a launch; further
+ * launches add to `combined`). */
+void bzamd_combine_columns_device(void* combined, void* product, unsigned field_id,
+                                  const struct bzamd_column_combination* c, void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
