@@ -222,6 +222,12 @@ def load():
         lib.bzamd_combine_columns.restype = None
         lib.bzamd_combine_columns_device.argtypes = [vp, vp, cu, vp, vp]
         lib.bzamd_combine_columns_device.restype = None
+    # (an older build selected with BLITZAR_AMD_LIB lacks these two)
+    if hasattr(lib, "bzamd_prepare_tiles_converted"):
+        lib.bzamd_prepare_tiles_converted.argtypes = []
+        lib.bzamd_prepare_tiles_converted.restype = u64
+        lib.bzamd_caller_table_reset.argtypes = []
+        lib.bzamd_caller_table_reset.restype = None
     _lib = lib
     return lib
 

@@ -444,7 +444,7 @@ u8* enqueue_commitments(api_state& st, device_state& ds, const curve_vtable& vt,
       vt.msm_resident(*ds.ctx, out_k, out_stride, projective_out, chunk, d_addends, ds.stream,
                       tables.windows != 0 ? &tables : nullptr);
     } else {
-      vt.msm(*ds.ctx, out_k, out_stride, projective_out, chunk, d_addends, nullptr, ds.stream);
+      vt.msm(*ds.ctx, out_k, out_stride, projective_out, chunk, d_addends, nullptr, ds.stream, false);
     }
     begin = end;
   }
@@ -677,7 +677,7 @@ u8* enqueue_commitments_row_pipeline(api_state& st, device_state& ds, const curv
         vt.prepare_addends(addends_k, r.api, rows, ds.stream);
         g_kernel_launches += 1;
       }
-      vt.msm(*ds.ctx, out_k, psize, true, mine, addends_k, nullptr, ds.stream);
+      vt.msm(*ds.ctx, out_k, psize, true, mine, addends_k, nullptr, ds.stream, false);
     } else {
       // a range of a resident set: the same rows of every window-table slice
       const void* d_addends =
@@ -703,7 +703,8 @@ u8* enqueue_commitments_row_pipeline(api_state& st, device_state& ds, const curv
     u8* out_b = d_out + (lead + batches[b].first) * static_cast<size_t>(out_stride);
     msm_context_defer_next_tail(ds.ctx);
     if (upload_generators) {
-      vt.msm(*ds.ctx, out_b, out_stride, projective_out, batch, d_addends_all, nullptr, ds.stream);
+      vt.msm(*ds.ctx, out_b, out_stride, projective_out, batch, d_addends_all, nullptr, ds.stream,
+             false);
     } else {
       vt.msm_resident(*ds.ctx, out_b, out_stride, projective_out, batch,
                       ds.builtin.rows_from(gens.offset, vt.resident_addend_size), ds.stream,
@@ -2090,6 +2091,41 @@ uint64_t bzamd_set_call_tables(int mode) {
   return built;
 }
 
+namespace {
+// every engine context of the backend with its HIP device: the current device's first
+std::vector<std::pair<int, msm_context*>> backend_contexts(api_state& st) {
+  int current = 0;
+  BZ_HIP_CHECK(hipGetDevice(&current));
+  std::vector<std::pair<int, msm_context*>> out{{current, st.context_for_current_device()}};
+  for (auto& d : st.devices) {
+    if (d->ctx != out[0].second) out.emplace_back(d->device, d->ctx);
+  }
+  return out;
+}
+} // namespace
+
+uint64_t bzamd_prepare_tiles_converted(void) {
+  api_state& st = state();
+  BZ_RELEASE_ASSERT(st.backend == SXT_GPU_BACKEND, "caller tables belong to the GPU backend");
+  const current_device_guard restore_callers_device;
+  uint64_t tiles = 0;
+  for (const auto& [device, ctx] : backend_contexts(st)) {
+    BZ_HIP_CHECK(hipSetDevice(device));
+    tiles += msm_context_tiles_converted(ctx);
+  }
+  return tiles;
+}
+
+void bzamd_caller_table_reset(void) {
+  api_state& st = state();
+  BZ_RELEASE_ASSERT(st.backend == SXT_GPU_BACKEND, "caller tables belong to the GPU backend");
+  const current_device_guard restore_callers_device;
+  for (const auto& [device, ctx] : backend_contexts(st)) {
+    BZ_HIP_CHECK(hipSetDevice(device));
+    msm_context_caller_table_reset(ctx);
+  }
+}
+
 void bzamd_set_segments(uint32_t log2_entries_per_accumulate_lane,
                         uint32_t log2_buckets_per_reduce_lane) {
   api_state& st = state();
@@ -2130,7 +2166,8 @@ void msm_device_in_passes(const curve_vtable& vt, msm_context* ctx, u8* out, boo
                       static_cast<const u8*>(d_addends) + addend_size * row_begin, stream, nullptr);
     } else {
       vt.msm(*ctx, d_partials + partial_bytes * k, psize, true, mine, nullptr,
-             static_cast<const u8*>(d_api_generators) + vt.api_generator_size * row_begin, stream);
+             static_cast<const u8*>(d_api_generators) + vt.api_generator_size * row_begin, stream,
+             false);
     }
   }
   if (projective_out) {
@@ -2155,8 +2192,8 @@ void msm_device(unsigned curve_id, void* out, uint32_t num_sequences,
   api_state& st = state();
   BZ_RELEASE_ASSERT(st.backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
   checked_columns cc = check_descriptors(descriptors, num_sequences);
-  generators = static_cast<const u8*>(generators) +
-               vt->api_generator_size * apply_generator_offsets(cc, generator_offsets, num_generators);
+  const u64 lowest = apply_generator_offsets(cc, generator_offsets, num_generators);
+  generators = static_cast<const u8*>(generators) + vt->api_generator_size * lowest;
   if (cc.generator_rows > g_max_rows_per_pass.load()) {
     t_pipeline_next = false; // a call of several passes completes on the caller's stream
     msm_device_in_passes(*vt, st.context_for_current_device(), static_cast<u8*>(out),
@@ -2165,9 +2202,10 @@ void msm_device(unsigned curve_id, void* out, uint32_t num_sequences,
     return;
   }
   apply_pipeline_request(st.context_for_current_device());
+  // (a window that starts at the caller's own pointer may use the context's caller table for it)
   vt->msm(*st.context_for_current_device(), static_cast<u8*>(out),
           static_cast<u32>(projective_out ? vt->projective_size : vt->output_size), projective_out,
-          cc.cols, nullptr, generators, static_cast<hipStream_t>(stream));
+          cc.cols, nullptr, generators, static_cast<hipStream_t>(stream), lowest == 0);
 }
 } // namespace
 
@@ -2333,7 +2371,7 @@ void bzamd_msm_multi_device(unsigned curve_id, void* const* commitments, uint32_
     if (begin == end) return;
     BZ_RELEASE_ASSERT(generators[d] != nullptr, "generators of a device that owns columns is null");
     const std::vector<host_column> mine(cc.cols.begin() + begin, cc.cols.begin() + end);
-    vt->msm(*ds.ctx, send[d], out_stride, false, mine, nullptr, generators[d], ds.stream);
+    vt->msm(*ds.ctx, send[d], out_stride, false, mine, nullptr, generators[d], ds.stream, true);
   });
 
   if (st.exchange_state == 1) {

@@ -185,6 +185,7 @@ msm_context* msm_context_new() {
   };
   flag("BLITZAR_AMD_OVERLAP_TAILS", ctx->overlap_tails);
   flag("BLITZAR_AMD_CALL_TABLES", ctx->call_tables);
+  flag("BLITZAR_AMD_CALLER_TABLE", ctx->caller_table);
   flag("BLITZAR_AMD_CALL_TABLE_OVERLAP", ctx->table_overlap);
   flag("BLITZAR_AMD_CALL_TABLE_WAVE_CHAIN", ctx->wave_chain);
   if (const char* v = std::getenv("BLITZAR_AMD_CALL_TABLE_BITS")) {
@@ -247,6 +248,21 @@ void msm_context_release(msm_context* ctx) { ctx->mu.unlock(); }
 void msm_context_defer_next_tail(msm_context* ctx) {
   std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   ctx->defer_tail = true;
+}
+u64 msm_context_tiles_converted(msm_context* ctx) {
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  if (ctx->tiles_converted == nullptr) return 0;
+  std::vector<unsigned long long> counters(kConvertedCounters * kConvertedCounterStride);
+  BZ_HIP_CHECK(hipDeviceSynchronize());
+  BZ_HIP_CHECK(hipMemcpy(counters.data(), ctx->tiles_converted, msm_context::kConvertedBytes,
+                         hipMemcpyDeviceToHost));
+  u64 count = 0;
+  for (u32 k = 0; k < kConvertedCounters; ++k) count += counters[k * kConvertedCounterStride];
+  return count;
+}
+void msm_context_caller_table_reset(msm_context* ctx) {
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  ctx->release_caller_slots();
 }
 void msm_context_join_tail(msm_context* ctx, hipStream_t stream) {
   std::lock_guard<std::recursive_mutex> lock(ctx->mu);

@@ -296,7 +296,7 @@ template <class C, class R = C, class H = C> struct curve_tu {
   }
   static void msm(msm_context& ctx, u8* d_out, u32 out_stride, bool projective_out,
                   const std::vector<host_column>& cols, const void* d_addends,
-                  const void* d_api_generators, hipStream_t stream) {
+                  const void* d_api_generators, hipStream_t stream, bool generators_keyed) {
     if (cols.empty()) return;
     std::lock_guard<std::recursive_mutex> lock(ctx.mu);
     configure_sort_kernels(ctx);
@@ -313,7 +313,8 @@ template <class C, class R = C, class H = C> struct curve_tu {
       }
     }
     msm_enqueue_locked<C>(ctx, d_out, out_stride, projective_out, cols,
-                          static_cast<const typename C::addend*>(d_addends), d_api_generators, stream);
+                          static_cast<const typename C::addend*>(d_addends), d_api_generators, stream,
+                          nullptr, false, generators_keyed);
   }
   static void prepare_addends(void* d_addends, const void* d_api_generators, u64 n,
                               hipStream_t stream) {

@@ -18,10 +18,13 @@ struct curve_vtable {
   size_t addend_size;        // resident addend
   size_t output_size;        // canonical commitment encoding
   size_t projective_size;    // raw projective element (fixed-base results, handle generators)
-  // enqueue a variable-base MSM; exactly one of d_addends / d_api_generators is used
+  // enqueue a variable-base MSM; exactly one of d_addends / d_api_generators is used.
+  // `generators_keyed`: d_api_generators is the caller's own generator pointer, not a row range of
+  // it -- the context may keep the converted generators in its caller table for that pointer and
+  // convert only the tiles whose bytes changed (engine.h, msm_context)
   void (*msm)(msm_context& ctx, u8* d_out, u32 out_stride, bool projective_out,
               const std::vector<host_column>& cols, const void* d_addends,
-              const void* d_api_generators, hipStream_t stream);
+              const void* d_api_generators, hipStream_t stream, bool generators_keyed);
   // C-ABI generators -> resident addends
   void (*prepare_addends)(void* d_addends, const void* d_api_generators, u64 n, hipStream_t stream);
   // projective elements (handle generators) -> resident addends (batch normalisation on device)
@@ -113,6 +116,11 @@ void msm_context_release(msm_context* ctx);
 // stages running on the context's own streams; `join_tail` makes `stream` wait for everything pending
 void msm_context_defer_next_tail(msm_context* ctx);
 void msm_context_join_tail(msm_context* ctx, hipStream_t stream);
+// caller tables (engine.h, msm_context), with the context's device current:
+// tiles of 64 generators converted into this context's caller tables so far (synchronises the device)
+u64 msm_context_tiles_converted(msm_context* ctx);
+// free the caller tables (the next call converts everything again)
+void msm_context_caller_table_reset(msm_context* ctx);
 // sorted entries per k_accumulate lane = 2^a (3..10), buckets per k_reduce lane = 2^r (1..8);
 // 0 = chosen per launch from its entry / bucket counts (plan.h)
 void msm_context_set_segments(msm_context* ctx, u32 log2_entries_per_accumulate_lane,

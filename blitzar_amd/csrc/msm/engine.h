@@ -189,6 +189,101 @@ struct msm_context {
     if (side != nullptr) return;
     BZ_HIP_CHECK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
   }
+  // Caller tables.  A service commits column after column against ONE array of caller generators;
+  // converting it again on every call (k_prepare_addends_staged: 160 MB in, 128 MB out at 2^20
+  // curve25519 rows) is work no result needs while the bytes stay what they were.  The context keeps
+  // the addends of the two caller pointers used last (LRU), keyed by (curve, addend size, pointer),
+  // each with a 128-bit digest per tile of 64 rows and one per row (msm/tile_digest.h): the prepare
+  // kernel still reads and hashes every byte on every call, and converts the tiles whose digest is
+  // not the stored one.  No sampling and nothing taken from the pointer alone: a changed tile is
+  // missed only on a collision of the digest.
+  //   * Tile t of a slot is rows 64 t .. 64 t + 63 from the keyed pointer, so calls of different
+  //     lengths at one pointer share their common prefix; a slot holds the largest row count seen
+  //     (hipMalloc on growth only, and growth starts the slot over: `valid_rows` = 0).
+  //   * Only an entry point that knows the call starts at the caller's own pointer offers it
+  //     (`generators_keyed` of curve_vtable::msm): row ranges of a call in several
+  //     passes and per-column offsets rebased to a lowest row above 0 convert into the arena as
+  //     before, and so do unaligned arrays and the batched (Z = 1) conversion.
+  //   * Order: a slot is read by k_accumulate and rewritten by a later call's prepare kernel, both on
+  //     their caller's stream, and every call on a context first orders its stream behind the
+  //     previous call's (order_after_previous): by induction behind every earlier call's.  No mark
+  //     of its own, and no stream handle kept in the slot.
+  //   * A call on a slot carves no addends from the arena; the pipeline's layout tag tells the two
+  //     carvings apart (a sequence that stays on its table is joined no more often than before).
+  //   * Memory: a slot takes the 128 B per generator (curve25519) the arena no longer holds, and 16 B
+  //     per generator and per tile for the digests.  It is kept until its pointer is the least
+  //     recently used of three, or bzamd_caller_table_reset; a second pointer means a second slot.
+  // BLITZAR_AMD_CALLER_TABLE=0 switches the tables off.
+  struct caller_slot {
+    unsigned curve = 0;
+    size_t addend_size = 0;
+    const void* key = nullptr;
+    void* addends = nullptr;
+    tile_digest* tiles = nullptr;
+    tile_digest* rows = nullptr;
+    size_t addend_bytes = 0; // capacity of `addends`
+    u64 capacity_rows = 0;   // ... of the digests
+    u64 valid_rows = 0;
+    u64 last_use = 0;
+    void release() {
+      for (void* p : {addends, static_cast<void*>(tiles), static_cast<void*>(rows)}) {
+        if (p != nullptr) (void)hipFree(p); // (waits for the kernels reading it)
+      }
+      *this = caller_slot{};
+    }
+  };
+  caller_slot caller_slots[2];
+  u64 caller_clock = 0;
+  bool caller_table = true;
+  // device counters of converting wavefronts (tests; kernels.h, kConvertedCounters)
+  static constexpr size_t kConvertedBytes =
+      sizeof(unsigned long long) * kConvertedCounters * kConvertedCounterStride;
+  unsigned long long* tiles_converted = nullptr;
+  void release_caller_slots() {
+    for (auto& s : caller_slots) s.release();
+  }
+  // The slot of (curve, addend size, key) with room for `rows` rows; nullptr when the device has no
+  // room for it (the call then converts into the arena).  `stream`: the call's.
+  caller_slot* caller_slot_for(unsigned curve, size_t addend_size, const void* key, u64 rows,
+                               hipStream_t stream) {
+    caller_slot* slot = nullptr;
+    for (auto& s : caller_slots) {
+      if (s.key == key && s.curve == curve && s.addend_size == addend_size) slot = &s;
+    }
+    if (slot == nullptr) {
+      slot = caller_slots[0].last_use <= caller_slots[1].last_use ? &caller_slots[0] : &caller_slots[1];
+      slot->curve = curve;
+      slot->addend_size = addend_size;
+      slot->key = key;
+      slot->valid_rows = 0;
+    }
+    if (tiles_converted == nullptr) {
+      BZ_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&tiles_converted), kConvertedBytes));
+      BZ_HIP_CHECK(hipMemsetAsync(tiles_converted, 0, kConvertedBytes, stream));
+    }
+    const size_t need_bytes = addend_size * (rows + 1);
+    if (need_bytes > slot->addend_bytes || rows > slot->capacity_rows) {
+      const caller_slot keep = *slot;
+      slot->release();
+      slot->curve = keep.curve;
+      slot->addend_size = keep.addend_size;
+      slot->key = keep.key;
+      const u64 cap = rows > keep.capacity_rows ? rows : keep.capacity_rows;
+      const size_t bytes = need_bytes > keep.addend_bytes ? need_bytes : keep.addend_bytes;
+      if (hipMalloc(&slot->addends, bytes) != hipSuccess ||
+          hipMalloc(reinterpret_cast<void**>(&slot->tiles), sizeof(tile_digest) * ((cap + 63) / 64)) !=
+              hipSuccess ||
+          hipMalloc(reinterpret_cast<void**>(&slot->rows), sizeof(tile_digest) * cap) != hipSuccess) {
+        (void)hipGetLastError();
+        slot->release();
+        return nullptr;
+      }
+      slot->addend_bytes = bytes;
+      slot->capacity_rows = cap;
+    }
+    slot->last_use = ++caller_clock;
+    return slot;
+  }
   u64 seq = 0;            // pipelined batches enqueued so far on this context
   u64 joined = 0;         // the caller's stream `joined_on` has waited for every batch below this
   hipStream_t joined_on = nullptr;
@@ -299,6 +394,8 @@ struct msm_context {
     }
     table_fork.destroy();
     table_ready.destroy();
+    release_caller_slots();
+    if (tiles_converted != nullptr) (void)hipFree(tiles_converted);
     for (hipStream_t s : {side, tail2, tail}) {
       if (s != nullptr) (void)hipStreamDestroy(s);
     }
@@ -395,7 +492,8 @@ static inline u32 partial_stride_of(const msm_plan& plan) {
 template <class C>
 void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool projective_out,
                        const msm_plan& plan, const typename C::addend* d_addends,
-                       const void* d_api_generators, hipStream_t stream, pipe_mode mode);
+                       const void* d_api_generators, hipStream_t stream, pipe_mode mode,
+                       msm_context::caller_slot* slot = nullptr);
 
 // Enqueue the MSM.  `d_addends` covers rows [0, max n); `d_out` receives one encoding per column
 // (`out_stride` bytes apart): canonical (`C::encode`) or raw projective when `projective_out`.
@@ -409,7 +507,8 @@ template <class C>
 void msm_enqueue_locked(msm_context& ctx, u8* d_out, u32 out_stride, bool projective_out,
                         const std::vector<host_column>& cols, const typename C::addend* d_addends,
                         const void* d_api_generators, hipStream_t stream,
-                        const window_table* tables = nullptr, bool force_tables = false);
+                        const window_table* tables = nullptr, bool force_tables = false,
+                        bool generators_keyed = false);
 
 template <class C>
 void msm_enqueue(msm_context& ctx, u8* d_out, u32 out_stride, bool projective_out,
@@ -428,7 +527,7 @@ template <class C>
 void msm_enqueue_locked(msm_context& ctx, u8* d_out, u32 out_stride, bool projective_out,
                         const std::vector<host_column>& cols, const typename C::addend* d_addends,
                         const void* d_api_generators, hipStream_t stream,
-                        const window_table* tables, bool force_tables) {
+                        const window_table* tables, bool force_tables, bool generators_keyed) {
   // throughput mode is for latency-bound tails: with hundreds of columns k_reduce and k_horner
   // fill the machine themselves (plan.h, defer_max_columns), so such a call ignores the request
   // and completes on the caller's stream
@@ -437,6 +536,14 @@ void msm_enqueue_locked(msm_context& ctx, u8* d_out, u32 out_stride, bool projec
   pipe_mode mode;
   mode.piped = ctx.defer_tail && ctx.overlap_tails && nonempty_columns < ctx.tuning.defer_max_columns;
   ctx.defer_tail = false;
+  // caller generators that start at the caller's own pointer: the context's caller table for them
+  // (one slot for every batch of the call), and no addends in the arena
+  msm_context::caller_slot* slot = nullptr;
+  if (generators_keyed && ctx.caller_table && d_addends == nullptr && d_api_generators != nullptr &&
+      caller_table_applies<C>(d_api_generators) && generator_rows_of(cols) != 0) {
+    slot = ctx.caller_slot_for(C::curve_id, sizeof(typename C::addend), d_api_generators,
+                               generator_rows_of(cols), stream);
+  }
   // a curve whose addends need a normalisation (the Z = 1 form of curve25519) runs against resident
   // sets only: its addends are never converted inside a call
   if constexpr (C::has_batched_prepare) {
@@ -463,7 +570,7 @@ void msm_enqueue_locked(msm_context& ctx, u8* d_out, u32 out_stride, bool projec
   std::vector<msm_plan> batches;
   std::vector<size_t> first_column;
   size_t need = 0;
-  const bool needs_addends = d_addends == nullptr;
+  const bool needs_addends = d_addends == nullptr && slot == nullptr;
   auto plan_range = [&](size_t begin, size_t end, size_t& bytes) {
     msm_plan p = make_msm_plan(std::vector<host_column>(cols.begin() + begin, cols.begin() + end),
                                tune, tables);
@@ -534,7 +641,7 @@ void msm_enqueue_locked(msm_context& ctx, u8* d_out, u32 out_stride, bool projec
   for (size_t k = 0; k < batches.size(); ++k) {
     ctx.arena.reset(need, stream);
     msm_enqueue_batch<C>(ctx, d_out + first_column[k] * static_cast<size_t>(out_stride), out_stride,
-                         projective_out, batches[k], d_addends, d_api_generators, stream, mode);
+                         projective_out, batches[k], d_addends, d_api_generators, stream, mode, slot);
   }
   ctx.mark_enqueued(stream);
 }
@@ -567,7 +674,8 @@ template <class C> struct batch_buffers {
 template <class C>
 void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool projective_out,
                        const msm_plan& plan, const typename C::addend* d_addends,
-                       const void* d_api_generators, hipStream_t stream, pipe_mode mode) {
+                       const void* d_api_generators, hipStream_t stream, pipe_mode mode,
+                       msm_context::caller_slot* slot) {
   using point = typename C::point;
   using addend = typename C::addend;
   const u32 num_tasks = static_cast<u32>(plan.tasks.size());
@@ -606,7 +714,8 @@ void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool project
                 static_cast<u64>(C::curve_id), static_cast<u64>(sizeof(addend)),
                 static_cast<u64>(d_addends == nullptr),
                 static_cast<u64>(mode.piped) | static_cast<u64>(plan.wide_digits) << 1 |
-                    static_cast<u64>(C::has_batched_prepare) << 2}) {
+                    static_cast<u64>(C::has_batched_prepare) << 2 |
+                    static_cast<u64>(slot != nullptr) << 3}) {
     layout = (layout ^ v) * 0x100000001b3ull;
   }
   if (ctx.any_pending() && layout != ctx.pipe_layout) ctx.join_all(stream);
@@ -666,7 +775,8 @@ void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool project
   // carve the arena: the same walk for every batch of a layout, this batch's sets picked out
   {
     addend* prepared =
-        d_addends == nullptr ? ctx.arena.take<addend>(plan.generator_rows + 1) : nullptr;
+        d_addends == nullptr && slot == nullptr ? ctx.arena.take<addend>(plan.generator_rows + 1)
+                                                : nullptr;
     void* digits = plan.wide_digits ? static_cast<void*>(ctx.arena.take<i32>(plan.total_entries + 8))
                                     : static_cast<void*>(ctx.arena.take<i16>(plan.total_entries + 8));
     u32* records = ctx.arena.take<u32>(plan.total_entries + 8);
@@ -679,7 +789,9 @@ void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool project
     u32* big_tasks = big_barrier + 1;
     u32* bucket_count = ctx.arena.take<u32>(2 * (plan.total_buckets + 1));
     u32* segment_bucket = ctx.arena.take<u32>(plan.total_segments + 1);
-    b.addends = d_addends == nullptr ? prepared : d_addends;
+    b.addends = d_addends != nullptr ? d_addends
+                : slot != nullptr    ? static_cast<const addend*>(slot->addends)
+                                     : prepared;
     b.digits = digits;
     b.records = records;
     b.sorted = sorted;
@@ -725,8 +837,17 @@ void msm_enqueue_batch(msm_context& ctx, u8* d_out, u32 out_stride, bool project
   // caller generators -> addends.  (Dealing this kernel's workgroups into the group sort's launch --
   // the one HBM-saturating kernel of the front inside the LDS-bound one -- was built and measured in
   // round 3: sort + conversion 0.171 -> 0.183 ms, profiles/round3_ab_front_fusion.log; removed.)
+  // (with a slot: into the context's table for the caller's pointer, and only the tiles whose bytes
+  // changed)
   if (d_addends == nullptr) {
     ctx.timer.timed(timing, 0, fs, [&] {
+      if (slot != nullptr) {
+        launch_prepare_addends_tabled<C>(
+            static_cast<addend*>(slot->addends), d_api_generators, plan.generator_rows,
+            caller_table_view{slot->tiles, slot->rows, slot->valid_rows, ctx.tiles_converted}, fs);
+        if (plan.generator_rows > slot->valid_rows) slot->valid_rows = plan.generator_rows;
+        return;
+      }
       launch_prepare_addends<C>(const_cast<addend*>(b.addends), d_api_generators,
                                 plan.generator_rows, fs);
     });

@@ -33,6 +33,7 @@
 #include "blitzar_amd/csrc/msm/curve_traits.h"
 #include "blitzar_amd/csrc/msm/plan.h"
 #include "blitzar_amd/csrc/msm/recode.h"
+#include "blitzar_amd/csrc/msm/tile_digest.h"
 
 namespace bz {
 
@@ -74,29 +75,109 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
-template <class C>
+// Table = true: the addends are a table the context keeps for one caller pointer (engine.h,
+// caller_slot), and a wavefront converts its tile only if the tile's bytes are not what they were
+// when it last did (msm/tile_digest.h).  Every byte is read and hashed on every call; what an
+// unchanged tile skips is the conversion, the second LDS pass and the store:
+//   * the 16-byte words a lane stages enter its digest state as they arrive; the finished states
+//     meet in a butterfly, and a tile whose digest equals `tiles[tile]` is done (the branch is wave-uniform);
+//   * otherwise every lane hashes its own row out of LDS and compares it with `rows[row]`: a tile
+//     that was last converted with another row count (a shorter or longer call at the same pointer)
+//     and whose rows are all unchanged is done as well;
+//   * otherwise the tile is converted as in the plain form, the digests of its rows and of the tile
+//     are rewritten and lane 0 counts the tile into `converted`.
+// A row's digest is only ever written together with its addend, and a tile's digest only when every
+// row it covers was converted or found unchanged in the same pass; rows from `valid_rows` on have
+// neither an addend nor a digest yet.
+struct caller_table_view {
+  tile_digest* tiles;  // [tile]
+  tile_digest* rows;   // [row]
+  u64 valid_rows;      // rows [0, valid_rows) have been converted into this table
+  unsigned long long* converted; // [kConvertedCounters], kConvertedCounterStride words apart
+};
+// the count of converting wavefronts, spread over cache lines by the tile's index: when every tile
+// of a launch converts, 16 K atomic adds on ONE address take longer than the conversion
+constexpr u32 kConvertedCounters = 256, kConvertedCounterStride = 16;
+template <class C, bool Table = false>
 __global__ void __launch_bounds__(256)
     k_prepare_addends_staged(typename C::addend* __restrict__ addends,
-                             const void* __restrict__ api_generators, u64 n) {
+                             const void* __restrict__ api_generators, u64 n,
+                             caller_table_view table) {
   using addend = typename C::addend;
   constexpr u32 G = static_cast<u32>(C::api_generator_size);
   constexpr u32 A = static_cast<u32>(sizeof(addend));
   static_assert(G % 8 == 0 && A % 16 == 0 && A <= G && (64 * G) % 16 == 0);
   __shared__ __attribute__((aligned(16))) u8 stage[4 * 64 * G];
-  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const u32 lane = threadIdx.x & 63;
+  // (wave-uniform by construction; said so, the tile's digest is fetched with a scalar load)
+  const u32 wave = Table ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
   const u64 first = (static_cast<u64>(blockIdx.x) * 4 + wave) * 64;
   if (first >= n) return;
   const u32 count = static_cast<u32>(n - first < 64 ? n - first : 64);
   u8* region = stage + wave * (64 * G);
   const u8* src = static_cast<const u8*>(api_generators) + first * G;
   const u32 in_bytes = count * G;
-  for (u32 off = lane * 16; off + 16 <= in_bytes; off += 64 * 16) {
-    *reinterpret_cast<uint4*>(region + off) = *reinterpret_cast<const uint4*>(src + off);
+  const u64 tile = first >> 6;
+  tile_digest state{}, stored{};
+  bool tile_known = false;
+  if constexpr (Table) {
+    tile_known = first < table.valid_rows;
+    if (tile_known) stored = table.tiles[tile];
+    state = digest_lane_begin(lane, count);
+  }
+  // (every load of the tile is issued before the first word is used: a wavefront that only
+  // compares digests is as long as its loads)
+  constexpr u32 kRounds = (64 * G / 16 + 63) / 64;
+  uint4 words[kRounds];
+#pragma unroll
+  for (u32 r = 0; r < kRounds; ++r) {
+    const u32 off = (r * 64 + lane) * 16;
+    if (off + 16 <= in_bytes) words[r] = *reinterpret_cast<const uint4*>(src + off);
+  }
+#pragma unroll
+  for (u32 r = 0; r < kRounds; ++r) {
+    const u32 off = (r * 64 + lane) * 16;
+    if (off + 16 <= in_bytes) {
+      const uint4 v = words[r];
+      *reinterpret_cast<uint4*>(region + off) = v;
+      if constexpr (Table) {
+        state = digest_absorb(state, off >> 4, v.x | static_cast<u64>(v.y) << 32,
+                              v.z | static_cast<u64>(v.w) << 32);
+      }
+    }
   }
   if ((in_bytes & 8) != 0 && lane == 0) { // G = 8 (mod 16) and an odd count
-    *reinterpret_cast<u64*>(region + in_bytes - 8) = *reinterpret_cast<const u64*>(src + in_bytes - 8);
+    const u64 v = *reinterpret_cast<const u64*>(src + in_bytes - 8);
+    *reinterpret_cast<u64*>(region + in_bytes - 8) = v;
+    if constexpr (Table) state = digest_absorb(state, in_bytes >> 4, v, 0);
+  }
+  tile_digest whole{}, mine{};
+  if constexpr (Table) {
+    state = digest_lane_end(state);
+    for (int m = 32; m >= 1; m >>= 1) {
+      state.a ^= __shfl_xor(state.a, m, 64);
+      state.b ^= __shfl_xor(state.b, m, 64);
+    }
+    whole = digest_finish(state, count);
+    if (tile_known && stored.a == whole.a && stored.b == whole.b) return;
   }
   wave_lds_fence();
+  if constexpr (Table) {
+    const bool known = lane < count && first + lane < table.valid_rows;
+    tile_digest was{};
+    if (known) was = table.rows[first + lane]; // (in flight while the row is hashed)
+    bool same = lane >= count;
+    if (lane < count) {
+      mine = digest_of_row(reinterpret_cast<const u64*>(region + lane * G), G, lane);
+      same = known && was.a == mine.a && was.b == mine.b;
+    }
+    if (__all(same)) {
+      // (a whole tile takes the short way again next time; a partial one leaves the entry to the
+      // longer call that wrote it)
+      if (count == 64 && lane == 0) table.tiles[tile] = whole;
+      return;
+    }
+  }
   addend a;
   if (lane < count) a = C::make_addend(region, lane);
   wave_lds_fence(); // every lane has read its generator: the region is free
@@ -106,6 +187,13 @@ __global__ void __launch_bounds__(256)
   const u32 out_bytes = count * A;
   for (u32 off = lane * 16; off < out_bytes; off += 64 * 16) {
     *reinterpret_cast<uint4*>(dst + off) = *reinterpret_cast<const uint4*>(region + off);
+  }
+  if constexpr (Table) {
+    if (lane < count) table.rows[first + lane] = mine;
+    if (lane == 0) {
+      table.tiles[tile] = whole;
+      atomicAdd(table.converted + (tile % kConvertedCounters) * kConvertedCounterStride, 1ull);
+    }
   }
 }
 
@@ -206,12 +294,28 @@ void launch_prepare_addends(typename C::addend* d_addends, const void* d_api_gen
                        dim3(kBatchPrepareThreads), 0, stream, d_addends, d_api_generators, n);
   } else if ((reinterpret_cast<uintptr_t>(d_api_generators) & 15) == 0 &&
              (reinterpret_cast<uintptr_t>(d_addends) & 15) == 0) {
-    hipLaunchKernelGGL((k_prepare_addends_staged<C>), dim3(ceil_div_u32(n, 256)), dim3(256), 0,
-                       stream, d_addends, d_api_generators, n);
+    hipLaunchKernelGGL((k_prepare_addends_staged<C, false>), dim3(ceil_div_u32(n, 256)), dim3(256),
+                       0, stream, d_addends, d_api_generators, n, caller_table_view{});
   } else {
     hipLaunchKernelGGL((k_prepare_addends<C>), dim3(ceil_div_u32(n, 256)), dim3(256), 0, stream,
                        d_addends, d_api_generators, n);
   }
+}
+
+// Can caller generators at this address go through a context's caller table?  (The staged kernel
+// carries the digests: curves whose conversion is the batched one, and arrays the 16-byte loads
+// cannot read, keep the per-call conversion.)
+template <class C> bool caller_table_applies(const void* d_api_generators) {
+  return !C::has_batched_prepare && (reinterpret_cast<uintptr_t>(d_api_generators) & 15) == 0;
+}
+// C-ABI generators -> the addends of a caller table (16-byte aligned like the generators): one
+// launch, like the plain conversion
+template <class C>
+void launch_prepare_addends_tabled(typename C::addend* d_addends, const void* d_api_generators,
+                                   u64 n, const caller_table_view& table, hipStream_t stream) {
+  if (n == 0) return;
+  hipLaunchKernelGGL((k_prepare_addends_staged<C, true>), dim3(ceil_div_u32(n, 256)), dim3(256), 0,
+                     stream, d_addends, d_api_generators, n, table);
 }
 
 //--------------------------------------------------------------------------------------------------

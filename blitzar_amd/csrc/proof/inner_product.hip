@@ -341,7 +341,7 @@ void enqueue_chain(msm_context& ctx, u8* l_vector, u8* r_vector, u8* ap_value, u
     col_l.generator_offset = mid;
     const host_column col_r =
         byte_column(reinterpret_cast<const u8*>(d_a + 4 * static_cast<u64>(mid)), mid + 1, 32, false);
-    vt.msm(ctx, d_lr, 32, false, {col_l, col_r}, nullptr, d_g, stream);
+    vt.msm(ctx, d_lr, 32, false, {col_l, col_r}, nullptr, d_g, stream, false);
     hipLaunchKernelGGL(k_round_challenge, dim3(1), dim3(64), 0, stream, l_vector + 32 * round,
                        r_vector + 32 * round, d_slot, transcript, d_lr, round == 0 ? n : u64{0});
     hipLaunchKernelGGL(k_fold_scalars, dim3(blocks), dim3(256), 0, stream, d_a,
@@ -747,7 +747,7 @@ void enqueue_verify_chain(msm_context& ctx, u32* verdict, u8* transcript, u64 n,
   host_column col_a = byte_column(d_s + 32 * kVerifyRowQ, 1 + np + 2 * rounds, 32, false);
   col_a.generator_offset = 1;
   const host_column col_b = byte_column(d_s, 2, 32, false);
-  curve25519_vtable().msm(ctx, d_encodings, 32, false, {col_a, col_b}, nullptr, d_g, stream);
+  curve25519_vtable().msm(ctx, d_encodings, 32, false, {col_a, col_b}, nullptr, d_g, stream, false);
   hipLaunchKernelGGL(k_verify_verdict, dim3(1), dim3(64), 0, stream, verdict, d_encodings, d_slot,
                      static_cast<u32>(rounds));
   BZ_HIP_CHECK(hipGetLastError());

@@ -111,6 +111,15 @@ void bzamd_set_window_bits(uint32_t window_bits);
  * Returns the number of tables built so far on the backend's contexts.  Results never depend on it.
  * Env: BLITZAR_AMD_CALL_TABLES=0, BLITZAR_AMD_CALL_TABLE_BITS=c, BLITZAR_AMD_CALL_TABLE_OVERLAP=0. */
 uint64_t bzamd_set_call_tables(int mode);
+/* Caller tables: bzamd_msm_device* over caller generators keeps the converted generators of the
+ * two generator pointers used last on a device, and a later call at the same pointer converts only
+ * the tiles of 64 generators whose bytes changed (every byte is read and compared by digest on
+ * every call).  Env: BLITZAR_AMD_CALLER_TABLE=0 converts everything on every call.
+ * bzamd_prepare_tiles_converted: tiles converted into the tables so far on the backend's contexts
+ * (synchronises their devices).  bzamd_caller_table_reset: free the tables.  For tests and tools;
+ * results never depend on either. */
+uint64_t bzamd_prepare_tiles_converted(void);
+void bzamd_caller_table_reset(void);
 /* Work per lane of the two bucket kernels, as log2 (0, the default, lets every launch choose from
  * its size): sorted entries per accumulation lane (2^3..2^10; 32 for a single column so that its
  * lanes fill the machine, up to 128 when hundreds of columns do -- every segment leaves one partial
