@@ -222,6 +222,13 @@ def load():
         lib.bzamd_combine_columns.restype = None
         lib.bzamd_combine_columns_device.argtypes = [vp, vp, cu, vp, vp]
         lib.bzamd_combine_columns_device.restype = None
+    if hasattr(lib, "bzamd_evaluate_columns_device"):
+        lib.bzamd_evaluate_columns.argtypes = [vp, cu, vp, vp]
+        lib.bzamd_evaluate_columns.restype = None
+        lib.bzamd_evaluate_columns_workspace_bytes.argtypes = [cu, cu, u64]
+        lib.bzamd_evaluate_columns_workspace_bytes.restype = u64
+        lib.bzamd_evaluate_columns_device.argtypes = [vp, cu, vp, vp, vp, u64, vp]
+        lib.bzamd_evaluate_columns_device.restype = None
     # (an older build selected with BLITZAR_AMD_LIB lacks these two)
     if hasattr(lib, "bzamd_prepare_tiles_converted"):
         lib.bzamd_prepare_tiles_converted.argtypes = []
@@ -786,6 +793,46 @@ def combine_columns_device(field_id, descriptors, coefficients_ptr, n, combined_
     load().bzamd_combine_columns_device(
         int(combined_ptr), None if product_ptr is None else int(product_ptr), field_id,
         ctypes.byref(c), None if stream is None else ctypes.c_void_p(int(stream)))
+
+
+class bzamd_column_evaluation(ctypes.Structure):
+    _fields_ = [("columns", ctypes.POINTER(sxt_sequence_descriptor)),
+                ("num_columns", ctypes.c_uint), ("n", ctypes.c_uint64)]
+
+
+def evaluate_columns(field_id, columns, vector, n):
+    """bzamd_evaluate_columns (host operands, either backend).  columns: as prove_sumcheck_columns;
+    vector: uint8 [n, 32], what mle_evaluation_vector returns
+    -> uint8 [num_columns, 32]: evaluations[j] = sum_i column_j[i] * vector[i]"""
+    descs, keep = make_descriptors(_column_pairs(columns))
+    vector = np.ascontiguousarray(vector, dtype=np.uint8)
+    evaluations = np.zeros((max(len(keep), 1), 32), dtype=np.uint8)
+    e = bzamd_column_evaluation(descs, len(keep), n)
+    load().bzamd_evaluate_columns(_ptr(evaluations), field_id, _ptr(vector), ctypes.byref(e))
+    return evaluations[:len(keep)]
+
+
+def evaluate_columns_workspace_bytes(field_id, num_columns, n):
+    """bzamd_evaluate_columns_workspace_bytes: needs no backend"""
+    return load().bzamd_evaluate_columns_workspace_bytes(field_id, num_columns, n)
+
+
+def evaluate_columns_device(field_id, descriptors, vector_ptr, n, evaluations_ptr, workspace_ptr,
+                            workspace_bytes, stream=None):
+    """bzamd_evaluate_columns_device: enqueue only.  descriptors: one (device_ptr, n_j, nbytes,
+    signed) per column, or a ready sxt_sequence_descriptor array (the one the MSM took); every
+    *_ptr is memory of the current device as an integer (None: a null pointer); `stream` a
+    hipStream_t as an integer (None: the default stream)."""
+    if isinstance(descriptors, ctypes.Array):
+        descs, num_columns = descriptors, len(descriptors)
+    else:
+        descs, num_columns = _device_descriptors(descriptors)
+    e = bzamd_column_evaluation(descs, num_columns, n)
+    load().bzamd_evaluate_columns_device(
+        None if evaluations_ptr is None else int(evaluations_ptr), field_id,
+        None if vector_ptr is None else int(vector_ptr), ctypes.byref(e),
+        None if workspace_ptr is None else int(workspace_ptr), workspace_bytes,
+        None if stream is None else ctypes.c_void_p(int(stream)))
 
 
 class MultiexpHandle:

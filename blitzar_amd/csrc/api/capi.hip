@@ -1970,6 +1970,42 @@ void bzamd_combine_columns_device(void* combined, void* product, unsigned field_
                                 device_form(stream).stream);
 }
 
+namespace {
+// the evaluation's columns, checked as in prove_sumcheck_columns_entry
+extern "C++" std::vector<proof::sumcheck_column> evaluation_form_columns(
+    const char* name, const void* evaluations, const void* vector,
+    const struct bzamd_column_evaluation* e) {
+  check_arguments(name, evaluations != nullptr && vector != nullptr && e != nullptr);
+  return checked_sumcheck_columns(e->columns, e->num_columns);
+}
+} // namespace
+
+void bzamd_evaluate_columns(void* evaluations, unsigned field_id, const void* vector,
+                            const struct bzamd_column_evaluation* e) {
+  const std::vector<proof::sumcheck_column> cols =
+      evaluation_form_columns("bzamd_evaluate_columns", evaluations, vector, e);
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::evaluate_columns(st, evaluations, field_id, vector,
+                          proof::column_evaluation{cols.data(), e->num_columns, e->n});
+}
+
+uint64_t bzamd_evaluate_columns_workspace_bytes(unsigned field_id, unsigned num_columns,
+                                                uint64_t n) {
+  return proof::evaluate_columns_workspace_bytes(field_id, num_columns, n);
+}
+
+void bzamd_evaluate_columns_device(void* evaluations, unsigned field_id, const void* vector,
+                                   const struct bzamd_column_evaluation* e, void* workspace,
+                                   uint64_t workspace_bytes, void* stream) {
+  const std::vector<proof::sumcheck_column> cols =
+      evaluation_form_columns("bzamd_evaluate_columns_device", evaluations, vector, e);
+  const hipStream_t on = device_form(stream).stream;
+  proof::evaluate_columns_device(evaluations, field_id, vector,
+                                 proof::column_evaluation{cols.data(), e->num_columns, e->n},
+                                 workspace, workspace_bytes, on);
+}
+
 //--------------------------------------------------------------------------------------------------
 // extensions (include/blitzar_amd.h)
 //--------------------------------------------------------------------------------------------------

@@ -33,4 +33,24 @@ void combine_columns(api_state& st, void* combined, void* product, unsigned fiel
 // everything but `c` and the columns array is memory of the current device; enqueue-only
 void combine_columns_device(void* combined, void* product, unsigned field_id,
                             const column_combination& c, hipStream_t stream);
+
+// bzamd_evaluate_columns: evaluations[j] = sum_{i < columns[j].n} column_j[i] vector[i], 32 bytes
+// each, canonical, any alignment.  `vector`: n x 32 bytes, entries meaning what a 32-byte column
+// element means, 8-byte aligned.  `columns`: num_columns of them, widths checked by the caller, on
+// the host
+struct column_evaluation {
+  const sumcheck_column* columns;
+  u32 num_columns;
+  u64 n;
+};
+// host operands, blocking, st.backend; GPU backend: the vector and the columns uploaded at their
+// own width to devices[0], whose lease the caller holds
+void evaluate_columns(api_state& st, void* evaluations, unsigned field_id, const void* vector,
+                      const column_evaluation& e);
+// the device form's workspace (the workgroups' partial sums); 0 for arguments the call would reject
+u64 evaluate_columns_workspace_bytes(unsigned field_id, u32 num_columns, u64 n);
+// everything but `e` and the columns array is memory of the current device; enqueue-only
+void evaluate_columns_device(void* evaluations, unsigned field_id, const void* vector,
+                             const column_evaluation& e, void* workspace, u64 workspace_bytes,
+                             hipStream_t stream);
 } // namespace bz::proof

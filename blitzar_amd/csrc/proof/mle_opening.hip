@@ -29,9 +29,23 @@
 // travel as kernel arguments, kCombineChunk at a time; a call with more columns launches the kernel
 // once per chunk and the later launches add to what `combined` holds, which is exact.  So the call
 // needs no memory beside its operands, however many columns it takes.
+//
+// The evaluation (bzamd_evaluate_columns*): evaluations[j] = <column_j, vector>, the producer of
+// the combination's `evaluations` for columns the sumcheck did not multiply.  Rows go to lanes
+// grid-stride; a lane fetches vector[i] once, as the raw residue of its 32 bytes, and multiplies
+// it into the raw row of each of the launch's kEvaluateChunk columns, one accumulator per column in
+// registers.  Neither operand is converted: the Montgomery product of two raw residues is short of
+// conversion(column's kind) * conversion(element) / R^2, one constant per column, which the finish
+// multiplies in once.  The additions are lazy, swept and reduced every kEvaluateSweep rows.  A
+// workgroup reduces each column in LDS and writes one partial per column to the caller's
+// workspace; k_evaluate_finish, one workgroup per column, adds a column's partials, applies the
+// constant and stores the bytes.  A call with more columns than a chunk launches the partial
+// kernel once per chunk and reads the vector again each time: 32 bytes a row and chunk, 4 bytes a
+// row and column at kEvaluateChunk = 8.
 #include "blitzar_amd/csrc/proof/mle_opening.h"
 
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "blitzar_amd/csrc/proof/sumcheck_columns.h"
@@ -46,6 +60,13 @@ constexpr u32 kMaxVariables = 30;
 constexpr u32 kCombineChunk = 32; // views per launch: 1 KiB of kernel arguments
 constexpr u32 kCombineThreads = 256;
 constexpr u32 kCombineBlocks = 4096;
+
+// columns whose accumulators one lane holds (72 registers): the most that leaves two wavefronts per
+// SIMD without scratch memory (249 / 227 VGPRs; 4: 148 / 126, 12 and more: one wavefront)
+constexpr u32 kEvaluateChunk = 8;
+constexpr u32 kEvaluateThreads = 256;
+constexpr u32 kEvaluateBlocks = 1024; // 4 workgroups per CU: twice what is resident
+constexpr u32 kEvaluateSweep = 4;     // rows a lane adds lazily between two carry sweeps
 
 struct vector_split {
   u32 lb, mb, hb;
@@ -179,6 +200,102 @@ __global__ void __launch_bounds__(64)
   if (threadIdx.x == 0) E::store(product, tree[0]);
 }
 
+struct evaluate_views {
+  column_view v[kEvaluateChunk];
+};
+
+// fn(constant j) for j = 0 .. kEvaluateChunk - 1, expanded at compile time: whatever fn indexes
+// with j is indexed by a constant, so a lane's accumulators stay in registers
+template <class Fn, u32... J>
+BZ_HD void for_each_of_chunk(std::integer_sequence<u32, J...>, Fn&& fn) {
+  (fn(std::integral_constant<u32, J>{}), ...);
+}
+template <class Fn> BZ_HD void for_each_of_chunk(Fn&& fn) {
+  for_each_of_chunk(std::make_integer_sequence<u32, kEvaluateChunk>{}, fn);
+}
+
+// partials[j * gridDim.x + block] = sum over the block's rows i < rows of raw(views.v[j][i]) *
+// raw(vector[i]) / R, j < count (normalised, V < 4; zero for a block or a column without rows), and
+// kinds[j] = whether column j holds 32-byte elements, for the constant the finish multiplies in.
+// `rows`: the longest column of the chunk.
+template <class E>
+__global__ void __launch_bounds__(kEvaluateThreads)
+    k_evaluate_columns(typename E::F::fe* __restrict__ partials, u32* __restrict__ kinds,
+                       const u64* __restrict__ vector, const evaluate_views views, u32 count,
+                       u64 rows) {
+  using F = typename E::F;
+  using fe = typename F::fe;
+  __shared__ fe tree[kEvaluateThreads];
+  if (blockIdx.x == 0 && threadIdx.x < count) {
+    kinds[threadIdx.x] = views.v[threadIdx.x].nbytes == E::element_bytes ? 1u : 0u;
+  }
+  fe acc[kEvaluateChunk];
+  for_each_of_chunk([&](auto j) { acc[j] = F::zero(); });
+  u32 pending = 0;
+  for (u64 i = static_cast<u64>(blockIdx.x) * kEvaluateThreads + threadIdx.x; i < rows;
+       i += static_cast<u64>(gridDim.x) * kEvaluateThreads) {
+    u64 w[4];
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) w[k] = vector[4 * i + k];
+    // the raw residue of the entry's bytes: normalised, V < 16 (2^256 - 1 over l)
+    const fe b = F::from_words(w);
+    for_each_of_chunk([&](auto j) {
+      // lazy: a product is normalised with V < 2, so between two sweeps a limb stays below
+      // (1 + kEvaluateSweep) 2^LB < 2^32 and the value below (4 + 2 kEvaluateSweep) p
+      if (j < count && i < views.v[j].n) {
+        acc[j] = F::add(acc[j], F::mul(load_raw<F>(views.v[j], i), b));
+      }
+    });
+    if (++pending == kEvaluateSweep) {
+      pending = 0;
+      for_each_of_chunk([&](auto j) { acc[j] = F::reduce(F::norm(acc[j])); });
+    }
+  }
+  for_each_of_chunk([&](auto j) {
+    if (j < count) {
+      tree[threadIdx.x] = F::reduce(F::norm(acc[j]));
+      __syncthreads();
+      for (u32 stride = kEvaluateThreads / 2; stride > 0; stride >>= 1) {
+        if (threadIdx.x < stride) {
+          tree[threadIdx.x] = fadd<F>(tree[threadIdx.x], tree[threadIdx.x + stride]);
+        }
+        __syncthreads();
+      }
+      if (threadIdx.x == 0) partials[static_cast<u64>(j) * gridDim.x + blockIdx.x] = tree[0];
+      __syncthreads();
+    }
+  });
+}
+
+// evaluations[j] = (the sum of column j's `blocks` partials) * conversion(column's kind) *
+// conversion(element: the vector's) / R^2, canonical; one workgroup per column.  A column without
+// rows has zero partials: 0.
+template <class E>
+__global__ void __launch_bounds__(kEvaluateThreads)
+    k_evaluate_finish(u8* __restrict__ evaluations, const typename E::F::fe* __restrict__ partials,
+                      const u32* __restrict__ kinds, u32 blocks) {
+  using F = typename E::F;
+  using fe = typename F::fe;
+  __shared__ fe tree[kEvaluateThreads];
+  const u64 j = blockIdx.x;
+  fe sum = F::zero();
+  for (u32 b = threadIdx.x; b < blocks; b += kEvaluateThreads) {
+    sum = fadd<F>(sum, partials[j * blocks + b]);
+  }
+  tree[threadIdx.x] = sum;
+  __syncthreads();
+  for (u32 stride = kEvaluateThreads / 2; stride > 0; stride >>= 1) {
+    if (threadIdx.x < stride) {
+      tree[threadIdx.x] = fadd<F>(tree[threadIdx.x], tree[threadIdx.x + stride]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const fe constant = F::mul(E::conversion(kinds[j] != 0), E::conversion(true));
+    E::store(evaluations + 32 * j, F::mul(tree[0], constant));
+  }
+}
+
 //--------------------------------------------------------------------------------------------------
 // checks
 //--------------------------------------------------------------------------------------------------
@@ -205,9 +322,53 @@ void check_combination(const void* combined, const column_combination& c) {
   }
 }
 
+void check_evaluation(const void* evaluations, const void* vector, const column_evaluation& e) {
+  BZ_RELEASE_ASSERT(e.num_columns >= 1, "the column evaluation needs at least one column");
+  BZ_RELEASE_ASSERT(evaluations != nullptr && vector != nullptr && e.columns != nullptr,
+                    "null argument to the column evaluation");
+  BZ_RELEASE_ASSERT(e.n >= 1 && e.n <= (u64{1} << 30), "the column evaluation needs 1 <= n <= 2^30");
+  BZ_RELEASE_ASSERT(reinterpret_cast<uintptr_t>(vector) % 8 == 0,
+                    "the evaluation vector must be 8-byte aligned");
+  for (u32 j = 0; j < e.num_columns; ++j) {
+    BZ_RELEASE_ASSERT(e.columns[j].n <= e.n, "an evaluated column is longer than n");
+  }
+}
+
+// workgroups of every k_evaluate_columns launch of a call over n rows
+u32 evaluate_blocks(u64 n) {
+  return static_cast<u32>(
+      std::min<u64>(kEvaluateBlocks, (n + kEvaluateThreads - 1) / kEvaluateThreads));
+}
+
+// the caller's workspace: partials[column][block], and the columns' kinds for the finish
+template <class F> struct evaluate_layout {
+  size_t partials, kinds, total;
+  evaluate_layout(u32 num_columns, u64 n) {
+    workspace_carver carve;
+    partials = carve.take(sizeof(typename F::fe) * evaluate_blocks(n) * num_columns);
+    kinds = carve.take(sizeof(u32) * num_columns);
+    total = carve.total();
+  }
+};
+
 //--------------------------------------------------------------------------------------------------
 // host backend: plain loops over the same element arithmetic
 //--------------------------------------------------------------------------------------------------
+template <class E> void evaluate_host(u8* evaluations, const u64* vector, const column_evaluation& e) {
+  using F = typename E::F;
+  using fe = typename F::fe;
+  for (u32 j = 0; j < e.num_columns; ++j) {
+    const column_view view = make_column_view(e.columns[j]);
+    fe acc = F::zero();
+    for (u64 i = 0; i < view.n; ++i) {
+      acc = fadd<F>(acc, F::mul(load_raw<F>(view, i), F::from_words(vector + 4 * i)));
+    }
+    const fe constant =
+        F::mul(E::conversion(view.nbytes == E::element_bytes), E::conversion(true));
+    E::store(evaluations + static_cast<size_t>(32) * j, F::mul(acc, constant));
+  }
+}
+
 template <class E>
 void evaluation_vector_host(u64* vector, const u8* point, u32 num_variables, u64 n) {
   using F = typename E::F;
@@ -292,6 +453,39 @@ void combine_enqueue(u64* combined, u8* product, const column_combination& c, hi
     BZ_HIP_CHECK(hipGetLastError());
     g_kernel_launches += 1;
   }
+}
+
+// ceil(num_columns / kEvaluateChunk) launches of the partial sums and one finish over all columns
+template <class E>
+void evaluate_enqueue(u8* evaluations, const u64* vector, const column_evaluation& e,
+                      void* workspace, u64 workspace_bytes, hipStream_t stream) {
+  using fe = typename E::F::fe;
+  const evaluate_layout<typename E::F> layout{e.num_columns, e.n};
+  BZ_RELEASE_ASSERT(workspace != nullptr && workspace_bytes >= layout.total,
+                    "the column evaluation workspace is too small");
+  u8* base = workspace_carver::aligned(workspace);
+  fe* d_partials = reinterpret_cast<fe*>(base + layout.partials);
+  u32* d_kinds = reinterpret_cast<u32*>(base + layout.kinds);
+  const u32 blocks = evaluate_blocks(e.n);
+  for (u32 first = 0; first < e.num_columns; first += kEvaluateChunk) {
+    const u32 count = std::min(kEvaluateChunk, e.num_columns - first);
+    evaluate_views views;
+    std::memset(&views, 0, sizeof(views));
+    u64 rows = 0;
+    for (u32 j = 0; j < count; ++j) {
+      views.v[j] = make_column_view(e.columns[first + j]);
+      rows = std::max(rows, views.v[j].n);
+    }
+    hipLaunchKernelGGL((k_evaluate_columns<E>), dim3(blocks), dim3(kEvaluateThreads), 0, stream,
+                       d_partials + static_cast<size_t>(first) * blocks, d_kinds + first, vector,
+                       views, count, rows);
+    BZ_HIP_CHECK(hipGetLastError());
+    g_kernel_launches += 1;
+  }
+  hipLaunchKernelGGL((k_evaluate_finish<E>), dim3(e.num_columns), dim3(kEvaluateThreads), 0, stream,
+                     evaluations, d_partials, d_kinds, blocks);
+  BZ_HIP_CHECK(hipGetLastError());
+  g_kernel_launches += 1;
 }
 } // namespace
 
@@ -388,6 +582,68 @@ void combine_columns(api_state& st, void* combined, void* product, unsigned fiel
     if (with_product) {
       BZ_HIP_CHECK(hipMemcpyAsync(product, d_product, 32, hipMemcpyDeviceToHost, stream));
     }
+    BZ_HIP_CHECK(hipStreamSynchronize(stream));
+    own.release();
+  });
+}
+
+u64 evaluate_columns_workspace_bytes(unsigned field_id, u32 num_columns, u64 n) {
+  if (field_id > 1 || num_columns == 0 || n == 0 || n > (u64{1} << 30)) return 0;
+  return with_elements(field_id, [&](auto elements) -> u64 {
+    return evaluate_layout<typename decltype(elements)::F>{num_columns, n}.total;
+  });
+}
+
+void evaluate_columns_device(void* evaluations, unsigned field_id, const void* vector,
+                             const column_evaluation& e, void* workspace, u64 workspace_bytes,
+                             hipStream_t stream) {
+  check_evaluation(evaluations, vector, e);
+  with_elements(field_id, [&](auto elements) {
+    evaluate_enqueue<decltype(elements)>(static_cast<u8*>(evaluations),
+                                         static_cast<const u64*>(vector), e, workspace,
+                                         workspace_bytes, stream);
+  });
+}
+
+void evaluate_columns(api_state& st, void* evaluations, unsigned field_id, const void* vector,
+                      const column_evaluation& e) {
+  check_evaluation(evaluations, vector, e);
+  with_elements(field_id, [&](auto elements) {
+    using E = decltype(elements);
+    if (st.backend != 2) {
+      evaluate_host<E>(static_cast<u8*>(evaluations), static_cast<const u64*>(vector), e);
+      return;
+    }
+    // the vector and the columns up at their own width, the device form, the evaluations down
+    hipStream_t stream = st.primary().stream;
+    BZ_HIP_CHECK(hipSetDevice(st.primary().device));
+    const size_t vector_bytes = static_cast<size_t>(32) * e.n;
+    const size_t evaluation_bytes = static_cast<size_t>(32) * e.num_columns;
+    const size_t workspace_bytes = evaluate_layout<typename E::F>{e.num_columns, e.n}.total;
+    size_t bytes = device_arena::padded(vector_bytes) + device_arena::padded(evaluation_bytes) +
+                   device_arena::padded(workspace_bytes);
+    for (u32 j = 0; j < e.num_columns; ++j) {
+      bytes += device_arena::padded(e.columns[j].n * e.columns[j].nbytes);
+    }
+    device_arena own;
+    own.reset(bytes, stream);
+    u64* d_vector = own.take<u64>(4 * e.n);
+    u8* d_evaluations = own.take<u8>(evaluation_bytes);
+    u8* d_workspace = own.take<u8>(workspace_bytes);
+    BZ_HIP_CHECK(hipMemcpyAsync(d_vector, vector, vector_bytes, hipMemcpyHostToDevice, stream));
+    std::vector<sumcheck_column> on_device(e.columns, e.columns + e.num_columns);
+    for (sumcheck_column& column : on_device) {
+      const size_t column_bytes = column.n * column.nbytes;
+      u8* staged = own.take<u8>(column_bytes);
+      if (column_bytes != 0) {
+        BZ_HIP_CHECK(hipMemcpyAsync(staged, column.data, column_bytes, hipMemcpyHostToDevice, stream));
+      }
+      column.data = staged;
+    }
+    const column_evaluation staged{on_device.data(), e.num_columns, e.n};
+    evaluate_enqueue<E>(d_evaluations, d_vector, staged, d_workspace, workspace_bytes, stream);
+    BZ_HIP_CHECK(hipMemcpyAsync(evaluations, d_evaluations, evaluation_bytes, hipMemcpyDeviceToHost,
+                                stream));
     BZ_HIP_CHECK(hipStreamSynchronize(stream));
     own.release();
   });

@@ -528,6 +528,45 @@ void bzamd_combine_columns(void* combined, void* product, unsigned field_id,
 void bzamd_combine_columns_device(void* combined, void* product, unsigned field_id,
                                   const struct bzamd_column_combination* c, void* stream);
 
+/* The MLE evaluations of typed columns, given the evaluation vector of the point:
+ *   evaluations[j] = sum_{i < columns[j].n} column_j[i] * vector[i],
+ * num_columns x 32 bytes, written canonical (no alignment needed).  With the vector of
+ * bzamd_mle_evaluation_vector this is the identity above, sum_i T_0[j][i] vector[i] =
+ * mle_evaluations[j], for any column, whether or not the sumcheck multiplied it: the evaluations
+ * bzamd_combine_columns takes.  The columns mean what they mean in bzamd_combine_columns and are
+ * validated by the same rule: columns[j].n <= n rows (longer aborts), rows past a column's end
+ * contribute nothing, n = 0 with data = NULL is a zero column (evaluation 0).  `vector`: n x 32
+ * bytes, an entry meaning what a 32-byte column element means (field 0 the little-endian integer
+ * mod l, field 1 Montgomery form x 2^256; unreduced entries are taken as given), 8-byte aligned
+ * (what bzamd_mle_evaluation_vector* writes; anything else aborts).  1 <= n <= 2^30,
+ * 1 <= num_columns (no upper limit); null evaluations, vector, e or columns abort.  None of the
+ * inputs is written. */
+struct bzamd_column_evaluation {
+  const struct sxt_sequence_descriptor* columns; /* num_columns descriptors */
+  unsigned num_columns;
+  uint64_t n;                                    /* rows of `vector` */
+};
+/* HOST operands (columns[j].data included), blocking, cpu and gpu backends.  The gpu backend
+ * uploads the vector and the columns at their own width, runs the device form on memory of the
+ * call's own and synchronises once. */
+void bzamd_evaluate_columns(void* evaluations, unsigned field_id, const void* vector,
+                            const struct bzamd_column_evaluation* e);
+/* What the device form needs as workspace: the partial sums of its workgroups.  Needs no backend;
+ * 0 for an unsupported field, num_columns = 0, n = 0 and n > 2^30. */
+uint64_t bzamd_evaluate_columns_workspace_bytes(unsigned field_id, unsigned num_columns, uint64_t n);
+/* DEVICE pointers on the current HIP device: evaluations, vector, every columns[j].data (any
+ * address) and workspace (any alignment; at least bzamd_evaluate_columns_workspace_bytes of the
+ * same arguments, less aborts).  HOST: the struct and the descriptors, which are read before the
+ * call returns.  gpu backend only.  The call only enqueues on `stream`: no synchronise, no
+ * allocation, no callback.  `vector` and the columns are read in stream order, so the call may
+ * follow bzamd_mle_evaluation_vector_device on the same stream with no synchronise in between, and
+ * a bzamd_combine_columns_device on the same stream may read `evaluations` right after it; a later
+ * call on the same stream may use the same workspace.  The descriptors travel as kernel arguments,
+ * 8 columns to a launch, and one more launch finishes every column. */
+void bzamd_evaluate_columns_device(void* evaluations, unsigned field_id, const void* vector,
+                                   const struct bzamd_column_evaluation* e, void* workspace,
+                                   uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

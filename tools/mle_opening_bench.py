@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Device timings of the opening bridge, warm, on one GPU: bzamd_mle_evaluation_vector_device and
-bzamd_combine_columns_device on resident operands, beside the bytes they move.
+"""Device timings of the opening bridge, warm, on one GPU: bzamd_mle_evaluation_vector_device,
+bzamd_combine_columns_device and bzamd_evaluate_columns_device on resident operands, beside the
+bytes they move.
 
     python tools/mle_opening_bench.py [--sizes 65536,1048576,4194304] [--samples 15] [--repeat 10]
                                       [--inner-product-sizes 65536,1048576] [--out FILE]
@@ -11,7 +12,11 @@ the same device:
   vector       the evaluation vector of a random point: 32 n bytes written;
   combine_i64  8 signed 8-byte columns of n rows with random coefficients and the product:
                64 n bytes read, 32 n written;
-  combine_32   8 columns of 32-byte elements: 256 n bytes read, 32 n written.
+  combine_32   8 columns of 32-byte elements: 256 n bytes read, 32 n written;
+  evaluate_i64 the evaluations of 16 signed 8-byte columns against a vector of n elements: 128 n
+               bytes of columns and, at 8 columns to a launch, the vector twice, 64 n bytes;
+  evaluate_32  the evaluations of 4 columns of 32-byte elements: 128 n bytes and the vector once.
+The evaluation legs also print their field products (one per row and column).
 A sample is `--repeat` calls between two device events on the stream, divided by the repeat count;
 printed per size and leg, one JSON line (appended to --out): median, min and max in microseconds,
 the bytes moved and the bandwidth the median implies.  Before the first sample the device runs the
@@ -37,6 +42,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 MODULUS = {0: 2**252 + 27742317777372353535851937790883648493,
            1: 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001}
 NUM_COLUMNS = 8
+EVALUATE_COLUMNS = {"evaluate_i64": 16, "evaluate_32": 4}
+EVALUATE_CHUNK = 8  # kEvaluateChunk of proof/mle_opening.hip: the vector is read once per chunk
 
 
 def elements(rng, field_id, count):
@@ -65,7 +72,7 @@ class Legs:
         # random bytes serve as i64 rows and, cut to 250 bits, as canonical elements of either
         # field: the arithmetic does not depend on the values
         self.i64 = [torch.randint(0, 256, (n, 8), dtype=torch.uint8, device=dev)
-                    for _ in range(NUM_COLUMNS)]
+                    for _ in range(EVALUATE_COLUMNS["evaluate_i64"])]
         self.wide = []
         for _ in range(NUM_COLUMNS):
             column = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device=dev)
@@ -75,17 +82,38 @@ class Legs:
         self.coefficients = {f: up(elements(rng, f, NUM_COLUMNS)) for f in (0, 1)}
         self.evaluations = {f: up(elements(rng, f, NUM_COLUMNS)) for f in (0, 1)}
         self.descriptors = {
-            "combine_i64": [(c.data_ptr(), n, 8, True) for c in self.i64],
-            "combine_32": [(c.data_ptr(), n, 32, False) for c in self.wide]}
+            "combine_i64": [(c.data_ptr(), n, 8, True) for c in self.i64[:NUM_COLUMNS]],
+            "combine_32": [(c.data_ptr(), n, 32, False) for c in self.wide],
+            "evaluate_i64": [(c.data_ptr(), n, 8, True) for c in self.i64],
+            "evaluate_32": [(c.data_ptr(), n, 32, False)
+                            for c in self.wide[:EVALUATE_COLUMNS["evaluate_32"]]]}
         self.bytes = {"vector": 32 * n + 32 * self.v,
                       "combine_i64": NUM_COLUMNS * 8 * n + 32 * n,
                       "combine_32": NUM_COLUMNS * 32 * n + 32 * n}
+        # the evaluation's vector (an element column serves) and its outputs and workspace
+        self.b = self.wide[-1]
+        self.evaluated = torch.empty((max(EVALUATE_COLUMNS.values()), 32), dtype=torch.uint8,
+                                     device=dev)
+        self.workspace = {}
+        for leg, columns in EVALUATE_COLUMNS.items():
+            width = 8 if leg == "evaluate_i64" else 32
+            chunks = (columns + EVALUATE_CHUNK - 1) // EVALUATE_CHUNK
+            self.bytes[leg] = columns * width * n + chunks * 32 * n + 32 * columns
+            for f in (0, 1):
+                size = api.evaluate_columns_workspace_bytes(f, columns, n)
+                self.workspace[(leg, f)] = (torch.empty(size, dtype=torch.uint8, device=dev), size)
 
     def call(self, leg, field_id, stream):
         if leg == "vector":
             self.api.mle_evaluation_vector_device(field_id, self.out.data_ptr(),
                                                   self.point[field_id].data_ptr(), self.v, self.n,
                                                   stream=stream)
+            return
+        if leg in EVALUATE_COLUMNS:
+            workspace, size = self.workspace[(leg, field_id)]
+            self.api.evaluate_columns_device(field_id, self.descriptors[leg], self.b.data_ptr(),
+                                             self.n, self.evaluated.data_ptr(), workspace.data_ptr(),
+                                             size, stream=stream)
             return
         self.api.combine_columns_device(field_id, self.descriptors[leg],
                                         self.coefficients[field_id].data_ptr(), self.n,
@@ -119,7 +147,9 @@ def main():
     assert hasattr(api.load(), "bzamd_combine_columns_device"), "this build has no opening bridge"
     sizes = [int(x) for x in args.sizes.split(",")]
     inner_product_sizes = [int(x) for x in args.inner_product_sizes.split(",") if x]
-    order = [(leg, f) for leg in ("vector", "combine_i64", "combine_32") for f in (0, 1)]
+    assert hasattr(api.load(), "bzamd_evaluate_columns_device"), "this build has no evaluation"
+    order = [(leg, f) for leg in ("vector", "combine_i64", "combine_32", "evaluate_i64",
+                                  "evaluate_32") for f in (0, 1)]
 
     def emit(rec):
         line = json.dumps(rec)
@@ -146,11 +176,16 @@ def main():
                 us[(leg, f)].append(legs.sample_us(leg, f, args.repeat))
         for leg, f in order:
             median = statistics.median(us[(leg, f)])
-            emit({"n": n, "leg": leg, "field_id": f, "columns": 0 if leg == "vector" else NUM_COLUMNS,
-                  "samples": args.samples, "repeat": args.repeat, "median_us": round(median, 2),
-                  "min_us": round(min(us[(leg, f)]), 2), "max_us": round(max(us[(leg, f)]), 2),
-                  "bytes": legs.bytes[leg],
-                  "gb_per_s": round(legs.bytes[leg] / median / 1e3, 1)})
+            columns = 0 if leg == "vector" else EVALUATE_COLUMNS.get(leg, NUM_COLUMNS)
+            rec = {"n": n, "leg": leg, "field_id": f, "columns": columns,
+                   "samples": args.samples, "repeat": args.repeat, "median_us": round(median, 2),
+                   "min_us": round(min(us[(leg, f)]), 2), "max_us": round(max(us[(leg, f)]), 2),
+                   "bytes": legs.bytes[leg],
+                   "gb_per_s": round(legs.bytes[leg] / median / 1e3, 1)}
+            if leg in EVALUATE_COLUMNS:
+                rec["field_products"] = columns * n
+                rec["products_per_ns"] = round(columns * n / median / 1e3, 2)
+            emit(rec)
         del legs
         if n in inner_product_sizes:
             worker.setup(n)
