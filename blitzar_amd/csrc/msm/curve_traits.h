@@ -117,6 +117,8 @@ struct ed25519_msm {
   using batch_fe = fe29;
   BZ_HD static fe29 batch_one() { return f29::one(); }
   BZ_HD static fe29 batch_mul(const fe29& a, const fe29& b) { return f29::mul(a, b); }
+  // zero mod p, whatever the representative (0, p, 2 p, ... in loose limbs)
+  BZ_HD static bool batch_is_zero(const fe29& a) { return f29::is_zero(a); }
   // the coordinate to invert for the affine form; edwards points never have Z = 0
   BZ_HD static fe29 batch_z(const point& p, bool& is_identity) {
     is_identity = false;
@@ -137,7 +139,11 @@ struct ed25519_msm {
   // 1 / z by the 64 lanes of one wavefront (every lane passes the same z and gets the result):
   // z^(p - 2) = (z^(2^252 - 3))^8 * z^3, the long exponentiation row-parallel (curve/ed16_wave.h)
   __device__ static fe29 batch_wave_invert(const fe29& z) {
-    const ed16w::lane_ctx c = ed16w::make_ctx(ed16w::wave_scratch());
+    return batch_wave_invert(z, ed16w::wave_scratch());
+  }
+  // (`lds`: the wavefront's scratch, for a kernel that has no LDS to spare for one of its own)
+  __device__ static fe29 batch_wave_invert(const fe29& z, ed16w::scratch* lds) {
+    const ed16w::lane_ctx c = ed16w::make_ctx(lds);
     const fe29 t = ed16w::pow22523(c, z);
     return f29::mul(f29::sqn(t, 3), f29::mul(f29::sq(z), z));
   }
@@ -216,8 +222,10 @@ struct ed25519_msm {
 #endif
 };
 
-// curve25519 against a *resident* generator set (registered once: built-in generators,
-// bzamd_generators, handles): Z = 1 addends of 128 bytes, 7 instead of 8 products per addition
+// curve25519 against generators that are normalised once and then kept: a *resident* set (built-in
+// generators, bzamd_generators, handles) or the context's caller table of a keyed caller pointer
+// (engine.h, caller_slot: a tile is normalised again only when its bytes change).  Z = 1 addends of
+// 128 bytes, 7 instead of 8 products per addition
 struct ed25519_niels_msm : ed25519_msm {
   using addend = ed29_niels;
   static constexpr int accumulate_launch_waves = accumulate_waves_per_simd;
@@ -249,6 +257,18 @@ struct ed25519_niels_msm : ed25519_msm {
   BZ_HD static fe29 batch_load_z(const void* api_generators, u64 i) {
     return f29::from_fe51(static_cast<const ed_point*>(api_generators)[i].Z);
   }
+  // X, Y, Z of generator i into registers (the staged prepare kernel: its LDS copy of the row is
+  // free once every lane has them)
+  BZ_HD static void batch_load_xyz(const void* api_generators, u64 i, fe29& big_x, fe29& big_y,
+                                   fe29& z) {
+    const ed_point& g = static_cast<const ed_point*>(api_generators)[i];
+    big_x = f29::from_fe51(g.X);
+    big_y = f29::from_fe51(g.Y);
+    z = f29::from_fe51(g.Z);
+  }
+#if defined(__HIPCC__)
+  using batch_scratch = ed16w::scratch;
+#endif
   BZ_HD static addend batch_make_addend(const void* api_generators, u64 i, const fe29& zinv) {
     const ed_point& g = static_cast<const ed_point*>(api_generators)[i];
     return niels_of(f29::from_fe51(g.X), f29::from_fe51(g.Y), zinv);

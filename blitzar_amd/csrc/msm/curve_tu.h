@@ -268,15 +268,19 @@ template <class C, class R = C, class H = C> struct curve_tu {
     return table;
   }
   // the model's choice for `cols` and, if it wants a table, the enqueued build (ctx.mu held)
+  // (`plain_is_resident_form`: without a table the call runs on a normalised caller slot, the
+  // table's own addend form -- an accumulated entry costs the same either way)
   static const typename R::addend* call_table_locked(msm_context& ctx,
                                                      const std::vector<host_column>& cols,
                                                      const void* d_api_generators,
-                                                     window_table& shape, hipStream_t stream) {
+                                                     window_table& shape, hipStream_t stream,
+                                                     bool plain_is_resident_form = false) {
     shape = window_table{};
     shape.windows = 0;
     if (!ctx.call_tables || d_api_generators == nullptr) return nullptr;
     const call_table_choice ch =
-        choose_call_table(cols, ctx.tuning, sizeof(typename R::addend), R::call_table_entry_cost,
+        choose_call_table(cols, ctx.tuning, sizeof(typename R::addend),
+                          plain_is_resident_form ? 1.0 : R::call_table_entry_cost,
                           ctx.force_call_table_bits);
     if (ch.shape.windows == 0) return nullptr;
     // every generator the columns read (their windows' union; the longest column when all offsets
@@ -304,11 +308,26 @@ template <class C, class R = C, class H = C> struct curve_tu {
     // many columns over the same caller generators (the reference's bucket_method2 regime): the
     // window table of the generators is built in the call and every column becomes one task
     if (d_addends == nullptr) {
+      // A curve whose resident form differs from the per-call one (curve25519: Z = 1) keeps the
+      // caller table of a keyed pointer in the resident form and runs the call with R's loop: the
+      // normalisation is paid per changed tile, not per call (k_prepare_addends_staged).  Whatever
+      // the caller table does not take -- unaligned arrays, row ranges, tables switched off --
+      // keeps C's per-call conversion and loop.
+      const bool resident_form = !std::is_same_v<C, R> && generators_keyed && ctx.caller_table &&
+                                 d_api_generators != nullptr &&
+                                 caller_table_applies<R>(d_api_generators) &&
+                                 generator_rows_of(cols) != 0;
       window_table shape;
-      const typename R::addend* table = call_table_locked(ctx, cols, d_api_generators, shape, stream);
+      const typename R::addend* table =
+          call_table_locked(ctx, cols, d_api_generators, shape, stream, resident_form);
       if (table != nullptr) {
         msm_enqueue_locked<R>(ctx, d_out, out_stride, projective_out, cols, table, nullptr, stream,
                               &shape, ctx.force_call_table_bits != 0);
+        return;
+      }
+      if (resident_form) {
+        msm_enqueue_locked<R>(ctx, d_out, out_stride, projective_out, cols, nullptr, d_api_generators,
+                              stream, nullptr, false, true);
         return;
       }
     }

@@ -192,7 +192,7 @@ struct msm_context {
   // Caller tables.  A service commits column after column against ONE array of caller generators;
   // converting it again on every call (k_prepare_addends_staged: 160 MB in, 128 MB out at 2^20
   // curve25519 rows) is work no result needs while the bytes stay what they were.  The context keeps
-  // the addends of the two caller pointers used last (LRU), keyed by (curve, addend size, pointer),
+  // the addends of the two caller pointers used last (LRU), keyed by (curve, addend form, pointer),
   // each with a 128-bit digest per tile of 64 rows and one per row (msm/tile_digest.h): the prepare
   // kernel still reads and hashes every byte on every call, and converts the tiles whose digest is
   // not the stored one.  No sampling and nothing taken from the pointer alone: a changed tile is
@@ -203,7 +203,12 @@ struct msm_context {
   //   * Only an entry point that knows the call starts at the caller's own pointer offers it
   //     (`generators_keyed` of curve_vtable::msm): row ranges of a call in several
   //     passes and per-column offsets rebased to a lowest row above 0 convert into the arena as
-  //     before, and so do unaligned arrays and the batched (Z = 1) conversion.
+  //     before, and so do unaligned arrays.
+  //   * curve25519 keeps a slot in the Z = 1 form (curve_tu.h, msm: the call then runs the 7-product
+  //     loop of resident sets).  A tile that converts is normalised, with one inversion per workgroup
+  //     of the prepare kernel, so the price of the form is paid where bytes change and not per call;
+  //     a caller who rewrites the array before every call pays it every time and can switch the
+  //     tables off.  The form is part of the key: no kernel reads a slot written in the other one.
   //   * Order: a slot is read by k_accumulate and rewritten by a later call's prepare kernel, both on
   //     their caller's stream, and every call on a context first orders its stream behind the
   //     previous call's (order_after_previous): by induction behind every earlier call's.  No mark
@@ -216,6 +221,7 @@ struct msm_context {
   // BLITZAR_AMD_CALLER_TABLE=0 switches the tables off.
   struct caller_slot {
     unsigned curve = 0;
+    bool normalised = false; // Z = 1 addends (curve25519)
     size_t addend_size = 0;
     const void* key = nullptr;
     void* addends = nullptr;
@@ -244,15 +250,19 @@ struct msm_context {
   }
   // The slot of (curve, addend size, key) with room for `rows` rows; nullptr when the device has no
   // room for it (the call then converts into the arena).  `stream`: the call's.
-  caller_slot* caller_slot_for(unsigned curve, size_t addend_size, const void* key, u64 rows,
-                               hipStream_t stream) {
+  caller_slot* caller_slot_for(unsigned curve, bool normalised, size_t addend_size, const void* key,
+                               u64 rows, hipStream_t stream) {
     caller_slot* slot = nullptr;
     for (auto& s : caller_slots) {
-      if (s.key == key && s.curve == curve && s.addend_size == addend_size) slot = &s;
+      if (s.key == key && s.curve == curve && s.normalised == normalised &&
+          s.addend_size == addend_size) {
+        slot = &s;
+      }
     }
     if (slot == nullptr) {
       slot = caller_slots[0].last_use <= caller_slots[1].last_use ? &caller_slots[0] : &caller_slots[1];
       slot->curve = curve;
+      slot->normalised = normalised;
       slot->addend_size = addend_size;
       slot->key = key;
       slot->valid_rows = 0;
@@ -266,6 +276,7 @@ struct msm_context {
       const caller_slot keep = *slot;
       slot->release();
       slot->curve = keep.curve;
+      slot->normalised = keep.normalised;
       slot->addend_size = keep.addend_size;
       slot->key = keep.key;
       const u64 cap = rows > keep.capacity_rows ? rows : keep.capacity_rows;
@@ -539,15 +550,21 @@ void msm_enqueue_locked(msm_context& ctx, u8* d_out, u32 out_stride, bool projec
   // caller generators that start at the caller's own pointer: the context's caller table for them
   // (one slot for every batch of the call), and no addends in the arena
   msm_context::caller_slot* slot = nullptr;
-  if (generators_keyed && ctx.caller_table && d_addends == nullptr && d_api_generators != nullptr &&
-      caller_table_applies<C>(d_api_generators) && generator_rows_of(cols) != 0) {
-    slot = ctx.caller_slot_for(C::curve_id, sizeof(typename C::addend), d_api_generators,
-                               generator_rows_of(cols), stream);
+  const bool caller_table_offered = generators_keyed && ctx.caller_table && d_addends == nullptr &&
+                                    d_api_generators != nullptr &&
+                                    caller_table_applies<C>(d_api_generators) &&
+                                    generator_rows_of(cols) != 0;
+  if (caller_table_offered) {
+    slot = ctx.caller_slot_for(C::curve_id, C::has_batched_prepare, sizeof(typename C::addend),
+                               d_api_generators, generator_rows_of(cols), stream);
   }
-  // a curve whose addends need a normalisation (the Z = 1 form of curve25519) runs against resident
-  // sets only: its addends are never converted inside a call
+  // a curve whose addends need a normalisation (the Z = 1 form of curve25519) never normalises a
+  // whole array inside a call: its addends are a resident set's or the caller table's, where only
+  // changed tiles are normalised (curve_tu.h, msm, offers nothing else; without device memory for
+  // the slot the call converts into the arena with the batched kernel)
   if constexpr (C::has_batched_prepare) {
-    BZ_RELEASE_ASSERT(d_addends != nullptr, "Z = 1 addends come from a resident generator set");
+    BZ_RELEASE_ASSERT(d_addends != nullptr || caller_table_offered,
+                      "Z = 1 addends come from a resident generator set or the context's caller table");
   }
   msm_tuning tune = ctx.tuning;
   tune.in_sequence = mode.piped;

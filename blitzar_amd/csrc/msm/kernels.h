@@ -30,6 +30,7 @@
 
 #include <utility>
 
+#include "blitzar_amd/csrc/msm/batch_tree.h"
 #include "blitzar_amd/csrc/msm/curve_traits.h"
 #include "blitzar_amd/csrc/msm/plan.h"
 #include "blitzar_amd/csrc/msm/recode.h"
@@ -63,6 +64,28 @@ __global__ void __launch_bounds__(256)
   addends[i] = C::make_addend(api_generators, i);
 }
 
+// Montgomery's trick across a workgroup of T lanes (T a power of two): `tree` has 2 T entries in
+// heap order (root 1, leaf T + lane).  tree_products: leaves -> products of every subtree, root in
+// tree[1].  tree_inverses: with tree[1] replaced by the inverse of the root, every node becomes
+// the inverse of its subtree's product (children get inv * sibling); the leaves end up holding the
+// inverse of each lane's own product.  (The levels themselves: msm/batch_tree.h.)
+template <class C, u32 T>
+__device__ __forceinline__ void tree_products(typename C::batch_fe* tree, u32 tid) {
+  __syncthreads();
+  for (u32 s = T / 2; s >= 1; s >>= 1) {
+    tree_product_step<C>(tree, s, tid);
+    __syncthreads();
+  }
+}
+template <class C, u32 T>
+__device__ __forceinline__ void tree_inverses(typename C::batch_fe* tree, u32 tid) {
+  __syncthreads();
+  for (u32 s = 1; s < T; s <<= 1) {
+    tree_inverse_step<C>(tree, s, tid);
+    __syncthreads();
+  }
+}
+
 // The same through LDS.  A lane reading its own generator touches ten (curve25519: 160-byte
 // elements) different 128-byte lines per load instruction of the wavefront, and its addend leaves
 // the same way: 288 MB moved at 4.2 TB/s.  Here every wavefront copies its 64 generators -- one
@@ -89,6 +112,25 @@ __device__ __forceinline__ void wave_lds_fence() {
 // A row's digest is only ever written together with its addend, and a tile's digest only when every
 // row it covers was converted or found unchanged in the same pass; rows from `valid_rows` on have
 // neither an addend nor a digest yet.
+//
+// A curve whose addends are the Z = 1 form (C::has_batched_prepare: curve25519's caller table)
+// converts a tile by normalising it, and the inversion is shared by the converting tiles of the
+// WORKGROUP -- up to 256 rows and one C::batch_wave_invert (~250 dependent squarings; at 2^20 rows 4096
+// such chains when everything converts, not 16 384).  Digesting is what it is above; then
+//   * a converting wavefront takes X, Y, Z of its rows into registers, after which no wavefront
+//     needs its staged bytes any more;
+//   * every wavefront -- those past `n` too, with no rows -- leaves a flag in the first word of its
+//     own region and meets the others at one barrier.  Nothing converts: the workgroup is done,
+//     which is the steady state of a caller whose generators stay what they are;
+//   * otherwise the product tree of the 256 lanes' Z and the scratch of the inversion take the
+//     staging region over (the kernel's 40 KiB are a quarter of a compute unit's LDS: one more byte
+//     would cost the hash-only launch its fourth workgroup).  Lanes without a row to convert
+//     contribute one(), and so does a row whose Z is zero mod p (tree_leaf, msm/batch_tree.h:
+//     callers pad with zero rows under zero scalars, and one zero in the product would silently
+//     spoil the other 255 rows; the row itself gets niels_of(X, Y, 1), gathered only under a
+//     non-zero digit, where no form of it means anything);
+//   * with the inverses back at the leaves the converting wavefronts store niels_of(X, Y, 1 / Z)
+//     through their region as in the plain form.  T is not read: it is recomputed from x y.
 struct caller_table_view {
   tile_digest* tiles;  // [tile]
   tile_digest* rows;   // [row]
@@ -104,6 +146,8 @@ __global__ void __launch_bounds__(256)
                              const void* __restrict__ api_generators, u64 n,
                              caller_table_view table) {
   using addend = typename C::addend;
+  constexpr bool Norm = Table && C::has_batched_prepare;
+  static_assert(Table || !C::has_batched_prepare, "Z = 1 addends outside a table: the batched kernel");
   constexpr u32 G = static_cast<u32>(C::api_generator_size);
   constexpr u32 A = static_cast<u32>(sizeof(addend));
   static_assert(G % 8 == 0 && A % 16 == 0 && A <= G && (64 * G) % 16 == 0);
@@ -112,8 +156,12 @@ __global__ void __launch_bounds__(256)
   // (wave-uniform by construction; said so, the tile's digest is fetched with a scalar load)
   const u32 wave = Table ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
   const u64 first = (static_cast<u64>(blockIdx.x) * 4 + wave) * 64;
-  if (first >= n) return;
-  const u32 count = static_cast<u32>(n - first < 64 ? n - first : 64);
+  if constexpr (!Norm) {
+    if (first >= n) return;
+  }
+  // (Norm: a wavefront past `n` has no rows and goes along to the workgroup's barriers)
+  const u32 count = first >= n ? 0 : static_cast<u32>(n - first < 64 ? n - first : 64);
+  bool convert = count != 0;
   u8* region = stage + wave * (64 * G);
   const u8* src = static_cast<const u8*>(api_generators) + first * G;
   const u32 in_bytes = count * G;
@@ -121,7 +169,7 @@ __global__ void __launch_bounds__(256)
   tile_digest state{}, stored{};
   bool tile_known = false;
   if constexpr (Table) {
-    tile_known = first < table.valid_rows;
+    tile_known = convert && first < table.valid_rows;
     if (tile_known) stored = table.tiles[tile];
     state = digest_lane_begin(lane, count);
   }
@@ -159,10 +207,13 @@ __global__ void __launch_bounds__(256)
       state.b ^= __shfl_xor(state.b, m, 64);
     }
     whole = digest_finish(state, count);
-    if (tile_known && stored.a == whole.a && stored.b == whole.b) return;
+    if (tile_known && stored.a == whole.a && stored.b == whole.b) {
+      if constexpr (!Norm) return;
+      convert = false;
+    }
   }
-  wave_lds_fence();
-  if constexpr (Table) {
+  if (convert) wave_lds_fence();
+  if (Table && convert) {
     const bool known = lane < count && first + lane < table.valid_rows;
     tile_digest was{};
     if (known) was = table.rows[first + lane]; // (in flight while the row is hashed)
@@ -175,12 +226,45 @@ __global__ void __launch_bounds__(256)
       // (a whole tile takes the short way again next time; a partial one leaves the entry to the
       // longer call that wrote it)
       if (count == 64 && lane == 0) table.tiles[tile] = whole;
-      return;
+      if constexpr (!Norm) return;
+      convert = false;
     }
   }
   addend a;
-  if (lane < count) a = C::make_addend(region, lane);
-  wave_lds_fence(); // every lane has read its generator: the region is free
+  if constexpr (Norm) {
+    using fe = typename C::batch_fe;
+    constexpr u32 T = 256;
+    static_assert(sizeof(fe) * 2 * T % 16 == 0 &&
+                  sizeof(fe) * 2 * T + sizeof(typename C::batch_scratch) <= sizeof(stage));
+    const bool live = convert && lane < count;
+    fe big_x, big_y, z;
+    if (live) C::batch_load_xyz(region, lane, big_x, big_y, z);
+    wave_lds_fence(); // every lane has read its generator: the region is free
+    if (lane == 0) *reinterpret_cast<u32*>(region) = convert ? 1u : 0u;
+    __syncthreads();
+    u32 any = 0;
+#pragma unroll
+    for (u32 w = 0; w < 4; ++w) any |= *reinterpret_cast<const u32*>(stage + w * (64 * G));
+    if (any == 0) return; // (the same four words in every lane of the workgroup)
+    __syncthreads(); // the flags are read: the tree may take their place
+    fe* tree = reinterpret_cast<fe*>(stage);
+    auto* scratch = reinterpret_cast<typename C::batch_scratch*>(stage + sizeof(fe) * 2 * T);
+    const u32 tid = threadIdx.x;
+    tree[T + tid] = live ? tree_leaf<C>(z, true) : C::batch_one();
+    tree_products<C, T>(tree, tid);
+    if (tid < 64) {
+      const fe inv = C::batch_wave_invert(tree[1], scratch); // all 64 lanes cooperate
+      if (tid == 0) tree[1] = inv;
+    }
+    tree_inverses<C, T>(tree, tid);
+    const fe zinv = tree[T + tid];
+    __syncthreads(); // every lane has its inverse: the bytes are staging regions again
+    if (!convert) return; // (no barrier from here on)
+    if (live) a = C::niels_of(big_x, big_y, zinv);
+  } else {
+    if (lane < count) a = C::make_addend(region, lane);
+    wave_lds_fence(); // every lane has read its generator: the region is free
+  }
   if (lane < count) *reinterpret_cast<addend*>(region + lane * A) = a;
   wave_lds_fence();
   u8* dst = reinterpret_cast<u8*>(addends + first);
@@ -197,7 +281,9 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// curve25519: caller generators arrive as projective element_p3 (any Z).  Normalising them to
+// curve25519: generators arrive as projective element_p3 (any Z); this is the normalisation of a
+// whole resident set in one launch (a caller table normalises tile by tile, in
+// k_prepare_addends_staged above, with the same tree).  Normalising them to
 // Z = 1 lets k_accumulate run the 7-product addition on 128-byte raw-limb rows (ed29_niels: nothing
 // to unpack) instead of the 8-product one -- 16 additions per generator saved one product each --
 // but costs an inversion per generator unless the inversions are shared: a workgroup takes
@@ -217,33 +303,6 @@ template <u32 N, class F> __device__ __forceinline__ void static_for(F&& f) {
     (f(std::integral_constant<u32, J>{}), ...);
   }(std::make_integer_sequence<u32, N>{});
 }
-// Montgomery's trick across a workgroup of T lanes (T a power of two): `tree` has 2 T entries in
-// heap order (root 1, leaf T + lane).  tree_products: leaves -> products of every subtree, root in
-// tree[1].  tree_inverses: with tree[1] replaced by the inverse of the root, every node becomes
-// the inverse of its subtree's product (children get inv * sibling); the leaves end up holding the
-// inverse of each lane's own product.
-template <class C, u32 T>
-__device__ __forceinline__ void tree_products(typename C::batch_fe* tree, u32 tid) {
-  __syncthreads();
-  for (u32 s = T / 2; s >= 1; s >>= 1) {
-    if (tid < s) tree[s + tid] = C::batch_mul(tree[2 * (s + tid)], tree[2 * (s + tid) + 1]);
-    __syncthreads();
-  }
-}
-template <class C, u32 T>
-__device__ __forceinline__ void tree_inverses(typename C::batch_fe* tree, u32 tid) {
-  __syncthreads();
-  for (u32 s = 1; s < T; s <<= 1) {
-    if (tid < s) {
-      const u32 i = s + tid;
-      const typename C::batch_fe inv = tree[i], left = tree[2 * i], right = tree[2 * i + 1];
-      tree[2 * i] = C::batch_mul(inv, right);
-      tree[2 * i + 1] = C::batch_mul(inv, left);
-    }
-    __syncthreads();
-  }
-}
-
 template <class C>
 __global__ void __launch_bounds__(kBatchPrepareThreads, 1)
     k_prepare_addends_batched(typename C::addend* __restrict__ addends,
@@ -303,10 +362,9 @@ void launch_prepare_addends(typename C::addend* d_addends, const void* d_api_gen
 }
 
 // Can caller generators at this address go through a context's caller table?  (The staged kernel
-// carries the digests: curves whose conversion is the batched one, and arrays the 16-byte loads
-// cannot read, keep the per-call conversion.)
+// carries the digests: arrays the 16-byte loads cannot read keep the per-call conversion.)
 template <class C> bool caller_table_applies(const void* d_api_generators) {
-  return !C::has_batched_prepare && (reinterpret_cast<uintptr_t>(d_api_generators) & 15) == 0;
+  return (reinterpret_cast<uintptr_t>(d_api_generators) & 15) == 0;
 }
 // C-ABI generators -> the addends of a caller table (16-byte aligned like the generators): one
 // launch, like the plain conversion
