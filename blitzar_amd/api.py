@@ -229,6 +229,22 @@ def load():
         lib.bzamd_evaluate_columns_workspace_bytes.restype = u64
         lib.bzamd_evaluate_columns_device.argtypes = [vp, cu, vp, vp, vp, u64, vp]
         lib.bzamd_evaluate_columns_device.restype = None
+    if hasattr(lib, "bzamd_combine_commitments_device"):
+        lib.bzamd_verify_sumcheck_device.argtypes = [vp, vp, vp, vp, cu, vp, cu, cu, cu, vp]
+        lib.bzamd_verify_sumcheck_device.restype = None
+        lib.bzamd_check_sumcheck_evaluations.argtypes = [cu, vp, vp, cu, vp, vp, cu, cu]
+        lib.bzamd_check_sumcheck_evaluations.restype = ctypes.c_int
+        lib.bzamd_check_sumcheck_evaluations_workspace_bytes.argtypes = [cu, cu, cu]
+        lib.bzamd_check_sumcheck_evaluations_workspace_bytes.restype = u64
+        lib.bzamd_check_sumcheck_evaluations_device.argtypes = [vp, cu, vp, vp, cu, vp, vp, cu, cu,
+                                                                cu, vp, u64, vp]
+        lib.bzamd_check_sumcheck_evaluations_device.restype = None
+        lib.bzamd_combine_commitments.argtypes = [vp, vp, vp, u64]
+        lib.bzamd_combine_commitments.restype = ctypes.c_int
+        lib.bzamd_combine_commitments_workspace_bytes.argtypes = [u64]
+        lib.bzamd_combine_commitments_workspace_bytes.restype = u64
+        lib.bzamd_combine_commitments_device.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp]
+        lib.bzamd_combine_commitments_device.restype = None
     # (an older build selected with BLITZAR_AMD_LIB lacks these two)
     if hasattr(lib, "bzamd_prepare_tiles_converted"):
         lib.bzamd_prepare_tiles_converted.argtypes = []
@@ -597,6 +613,89 @@ def verify_sumcheck(field_id, claimed_sum, round_polynomials, transcript):
     ok = load().bzamd_verify_sumcheck(_ptr(expected), _ptr(point), _ptr(t), field_id, _ptr(polys),
                                       num_variables, length - 1)
     return bool(ok), expected, point, t
+
+
+def _stream(stream):
+    return None if stream is None else ctypes.c_void_p(int(stream))
+
+
+def verify_sumcheck_device(field_id, num_variables, round_degree, num_proofs,
+                           round_polynomials_ptr, expected_sums_ptr, evaluation_points_ptr,
+                           transcripts_ptr, verdicts_ptr, stream=None):
+    """bzamd_verify_sumcheck_device: enqueue only.  `num_proofs` proofs of one shape back to back;
+    every *_ptr is memory of the current device as an integer (torch: tensor.data_ptr()): per proof
+    num_variables x (round_degree + 1) x 32 bytes of polynomials, 32 of expected sum (in / out),
+    num_variables x 32 of evaluation point (out), 203 of transcript (in / out) and one uint32
+    verdict (out)."""
+    load().bzamd_verify_sumcheck_device(int(verdicts_ptr), int(expected_sums_ptr),
+                                        int(evaluation_points_ptr), int(transcripts_ptr), field_id,
+                                        int(round_polynomials_ptr), num_variables, round_degree,
+                                        num_proofs, _stream(stream))
+
+
+def _statement(field_id, product_table, product_terms):
+    table = np.ascontiguousarray(product_table, dtype=np.uint8)
+    terms = np.ascontiguousarray(product_terms, dtype=np.uint32)
+    return table, terms, table.size // SUMCHECK_PRODUCT_STRIDE[field_id]
+
+
+def check_sumcheck_evaluations(field_id, expected_sum, mle_evaluations, product_table,
+                               product_terms):
+    """bzamd_check_sumcheck_evaluations (host operands) -> bool.  mle_evaluations: uint8
+    [num_mles, 32]; the table and the terms as the prover takes them"""
+    table, terms, num_products = _statement(field_id, product_table, product_terms)
+    evaluations = np.ascontiguousarray(mle_evaluations, dtype=np.uint8).reshape(-1, 32)
+    expected = np.ascontiguousarray(expected_sum, dtype=np.uint8)
+    return bool(load().bzamd_check_sumcheck_evaluations(
+        field_id, _ptr(expected), _ptr(evaluations), evaluations.shape[0], _ptr(table), _ptr(terms),
+        num_products, terms.size))
+
+
+def check_sumcheck_evaluations_workspace_bytes(field_id, num_products, num_product_terms):
+    """bytes of device workspace bzamd_check_sumcheck_evaluations_device needs (0 for counts the
+    call rejects); needs no backend"""
+    return load().bzamd_check_sumcheck_evaluations_workspace_bytes(field_id, num_products,
+                                                                   num_product_terms)
+
+
+def check_sumcheck_evaluations_device(field_id, num_mles, product_table, product_terms, num_proofs,
+                                      expected_sums_ptr, mle_evaluations_ptr, verdicts_ptr,
+                                      workspace_ptr, workspace_bytes, stream=None):
+    """bzamd_check_sumcheck_evaluations_device: enqueue only.  One statement (host arrays) for
+    `num_proofs` proofs; every *_ptr is memory of the current device as an integer: num_proofs x 32
+    bytes of expected sums, num_proofs x num_mles x 32 of evaluations, num_proofs uint32 verdicts."""
+    table, terms, num_products = _statement(field_id, product_table, product_terms)
+    load().bzamd_check_sumcheck_evaluations_device(
+        int(verdicts_ptr), field_id, int(expected_sums_ptr), int(mle_evaluations_ptr), num_mles,
+        _ptr(table), _ptr(terms), num_products, terms.size, num_proofs, int(workspace_ptr),
+        workspace_bytes, _stream(stream))
+
+
+def combine_commitments(commitments, coefficients):
+    """bzamd_combine_commitments (host operands): commitments uint8 [K, 32] compressed, coefficients
+    uint8 [K, 32] -> (every encoding decoded, sum_j c_j C_j as one sxt_ristretto255, uint64 [20])"""
+    c = np.ascontiguousarray(commitments, dtype=np.uint8).reshape(-1, 32)
+    k = np.ascontiguousarray(coefficients, dtype=np.uint8).reshape(-1, 32)
+    assert c.shape == k.shape
+    out = np.zeros(20, dtype=np.uint64)
+    ok = load().bzamd_combine_commitments(_ptr(out), _ptr(c), _ptr(k), c.shape[0])
+    return bool(ok), out
+
+
+def combine_commitments_workspace_bytes(num_commitments):
+    """bytes of device workspace bzamd_combine_commitments_device needs (0 for 0 or more than 2^28
+    commitments); needs no backend"""
+    return load().bzamd_combine_commitments_workspace_bytes(num_commitments)
+
+
+def combine_commitments_device(num_commitments, commitments_ptr, coefficients_ptr, combined_ptr,
+                               valid_ptr, workspace_ptr, workspace_bytes, stream=None):
+    """bzamd_combine_commitments_device: enqueue only.  Every *_ptr is memory of the current device
+    as an integer: num_commitments x 32 bytes of encodings and of coefficients, 160 bytes of
+    `combined` (one sxt_ristretto255), one uint32 `valid`."""
+    load().bzamd_combine_commitments_device(int(combined_ptr), int(valid_ptr), int(commitments_ptr),
+                                            int(coefficients_ptr), num_commitments,
+                                            int(workspace_ptr), workspace_bytes, _stream(stream))
 
 
 class bzamd_sumcheck_columns(ctypes.Structure):

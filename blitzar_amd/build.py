@@ -36,6 +36,7 @@ SOURCES = [
     "proof/sumcheck_columns.hip",
     "proof/sumcheck_transcript.hip",
     "proof/mle_opening.hip",
+    "proof/verify_opening.hip",
     "api/capi.hip",
 ]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-I" + ROOT,

@@ -28,6 +28,7 @@
 #include "blitzar_amd/csrc/proof/sumcheck.h"
 #include "blitzar_amd/csrc/proof/sumcheck_transcript.h"
 #include "blitzar_amd/csrc/proof/transcript.h"
+#include "blitzar_amd/csrc/proof/verify_opening.h"
 #include "include/blitzar_amd.h"
 
 using namespace bz;
@@ -1919,6 +1920,101 @@ int bzamd_verify_sumcheck(void* expected_sum, void* evaluation_point,
                                 round_polynomials, num_variables, round_degree)
              ? 1
              : 0;
+}
+
+// the verifier's checks in front of the inner-product verifier (proof/verify_opening.hip).  The
+// device forms check their arguments before they ask for the backend
+void bzamd_verify_sumcheck_device(void* verdicts, void* expected_sums, void* evaluation_points,
+                                  void* transcripts, unsigned field_id,
+                                  const void* round_polynomials, unsigned num_variables,
+                                  unsigned round_degree, unsigned num_proofs, void* stream) {
+  check_arguments("bzamd_verify_sumcheck_device",
+                  verdicts != nullptr && expected_sums != nullptr && evaluation_points != nullptr &&
+                      transcripts != nullptr && round_polynomials != nullptr);
+  BZ_RELEASE_ASSERT(num_variables > 0 && round_degree > 0,
+                    "sumcheck verification needs num_variables > 0 and round_degree > 0");
+  BZ_RELEASE_ASSERT(round_degree <= 8, "round_degree must be in [1, 8]");
+  BZ_RELEASE_ASSERT(num_proofs > 0, "the sumcheck verifier needs at least one proof");
+  BZ_RELEASE_ASSERT(field_id <= 1, "unsupported field id");
+  proof::verify_sumcheck_device(verdicts, expected_sums, evaluation_points, transcripts, field_id,
+                                round_polynomials, num_variables, round_degree, num_proofs,
+                                device_form(stream).stream);
+}
+
+int bzamd_check_sumcheck_evaluations(unsigned field_id, const void* expected_sum,
+                                     const void* mle_evaluations, unsigned num_mles,
+                                     const void* product_table, const unsigned* product_terms,
+                                     unsigned num_products, unsigned num_product_terms) {
+  check_arguments("bzamd_check_sumcheck_evaluations",
+                  expected_sum != nullptr && mle_evaluations != nullptr &&
+                      product_table != nullptr && product_terms != nullptr);
+  return proof::check_sumcheck_evaluations(
+             field_id, expected_sum, mle_evaluations,
+             proof::evaluation_statement{product_table, product_terms, num_mles, num_products,
+                                         num_product_terms})
+             ? 1
+             : 0;
+}
+
+uint64_t bzamd_check_sumcheck_evaluations_workspace_bytes(unsigned field_id, unsigned num_products,
+                                                          unsigned num_product_terms) {
+  return proof::check_sumcheck_evaluations_workspace_bytes(field_id, num_products,
+                                                           num_product_terms);
+}
+
+void bzamd_check_sumcheck_evaluations_device(void* verdicts, unsigned field_id,
+                                             const void* expected_sums, const void* mle_evaluations,
+                                             unsigned num_mles, const void* product_table,
+                                             const unsigned* product_terms, unsigned num_products,
+                                             unsigned num_product_terms, unsigned num_proofs,
+                                             void* workspace, uint64_t workspace_bytes,
+                                             void* stream) {
+  check_arguments("bzamd_check_sumcheck_evaluations_device",
+                  verdicts != nullptr && expected_sums != nullptr && mle_evaluations != nullptr &&
+                      product_table != nullptr && product_terms != nullptr && workspace != nullptr);
+  BZ_RELEASE_ASSERT(num_proofs > 0, "the evaluation check needs at least one proof");
+  BZ_RELEASE_ASSERT(field_id <= 1, "unsupported field id");
+  const hipStream_t on = device_form(stream).stream;
+  proof::check_sumcheck_evaluations_device(
+      verdicts, field_id, expected_sums, mle_evaluations,
+      proof::evaluation_statement{product_table, product_terms, num_mles, num_products,
+                                  num_product_terms},
+      num_proofs, workspace, workspace_bytes, on);
+}
+
+int bzamd_combine_commitments(struct sxt_ristretto255* combined,
+                              const struct sxt_ristretto255_compressed* commitments,
+                              const void* coefficients, uint64_t num_commitments) {
+  check_arguments("bzamd_combine_commitments",
+                  combined != nullptr && commitments != nullptr && coefficients != nullptr);
+  BZ_RELEASE_ASSERT(num_commitments >= 1 && num_commitments <= proof::kMaxCombinedCommitments,
+                    "the commitment combination needs 1 <= num_commitments <= 2^28");
+  (void)state(); // an initialised backend, whichever: the arithmetic is the host's
+  return proof::combine_commitments(combined, reinterpret_cast<const u8*>(commitments),
+                                    static_cast<const u8*>(coefficients), num_commitments)
+             ? 1
+             : 0;
+}
+
+uint64_t bzamd_combine_commitments_workspace_bytes(uint64_t num_commitments) {
+  return proof::combine_commitments_workspace_bytes(num_commitments);
+}
+
+void bzamd_combine_commitments_device(void* combined, void* valid, const void* commitments,
+                                      const void* coefficients, uint64_t num_commitments,
+                                      void* workspace, uint64_t workspace_bytes, void* stream) {
+  check_arguments("bzamd_combine_commitments_device",
+                  combined != nullptr && valid != nullptr && commitments != nullptr &&
+                      coefficients != nullptr && workspace != nullptr);
+  BZ_RELEASE_ASSERT(num_commitments >= 1 && num_commitments <= proof::kMaxCombinedCommitments,
+                    "the commitment combination needs 1 <= num_commitments <= 2^28");
+  // the current device, the caller's stream and workspace, no lease: as the inner-product verifier
+  api_state& st = state();
+  BZ_RELEASE_ASSERT(st.backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
+  proof::combine_commitments_device(*st.context_for_current_device(), combined, valid,
+                                    static_cast<const u8*>(commitments),
+                                    static_cast<const u8*>(coefficients), num_commitments, workspace,
+                                    workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 // from the sumcheck's outputs to the inner-product prover's inputs (proof/mle_opening.hip)

@@ -425,6 +425,76 @@ int bzamd_verify_sumcheck(void* expected_sum, void* evaluation_point, struct sxt
                           unsigned field_id, const void* round_polynomials, unsigned num_variables,
                           unsigned round_degree);
 
+/* The same verifier on device-resident proofs: num_proofs independent proofs of one shape, laid out
+ * back to back at byte granularity.  DEVICE pointers on the current HIP device, per proof:
+ * round_polynomials num_variables x (round_degree + 1) x 32 bytes (read in stream order, never
+ * written), expected_sums 32 bytes (in / out), evaluation_points num_variables x 32 bytes (out),
+ * transcripts 203 bytes (in / out, used in place; proof i's transcript is at byte 203 i) and
+ * verdicts one uint32_t (out).  Proof i is exactly bzamd_verify_sumcheck on the same bytes:
+ * verdicts[i] is 1, or 0 at the first failing round -- the proof's expected_sum, the rows of its
+ * evaluation point already written and its transcript are then as the rounds before it left them,
+ * later rows of the point are not written.  One wavefront per proof, one kernel launch for the
+ * batch, no workspace.  gpu backend only.  The call only enqueues on `stream`: no synchronise, no
+ * allocation, no callback.  Aborts before anything is launched: NULL pointers, num_variables == 0,
+ * round_degree == 0 or > 8, num_proofs == 0, an unsupported field id. */
+void bzamd_verify_sumcheck_device(void* verdicts, void* expected_sums, void* evaluation_points,
+                                  void* transcripts, unsigned field_id,
+                                  const void* round_polynomials, unsigned num_variables,
+                                  unsigned round_degree, unsigned num_proofs, void* stream);
+
+/* The check the rounds' verifier leaves to its caller: 1 iff
+ *   sum_p mult_p prod_{j in terms_p} mle_evaluations[j] == expected_sum
+ * on canonical values (unreduced 32-byte inputs are taken as given), else 0.  expected_sum is what
+ * bzamd_verify_sumcheck* left, mle_evaluations the num_mles elements the prover returned.
+ * product_table and product_terms are those of `sumcheck_descriptor` ({multiplier; unsigned
+ * length} entries of 36 bytes for field 0, 40 for field 1), validated as the prover validates
+ * them, except that no round degree bounds a product: it needs at least one term.  Aborts: NULL
+ * pointers, num_mles == 0, num_products == 0, a product without terms, a term >= num_mles,
+ * num_product_terms that is not the sum of the lengths, an unsupported field id.
+ * HOST operands, host arithmetic, needs no backend. */
+int bzamd_check_sumcheck_evaluations(unsigned field_id, const void* expected_sum,
+                                     const void* mle_evaluations, unsigned num_mles,
+                                     const void* product_table, const unsigned* product_terms,
+                                     unsigned num_products, unsigned num_product_terms);
+/* The device form for num_proofs proofs of one statement.  DEVICE pointers on the current HIP
+ * device: expected_sums (num_proofs x 32 bytes), mle_evaluations (num_proofs x num_mles x 32 bytes;
+ * both read in stream order, never written), verdicts (num_proofs x uint32_t, out) and workspace
+ * (at least bzamd_check_sumcheck_evaluations_workspace_bytes of the same field and counts; less
+ * aborts; any alignment; a later call on the same stream may reuse it).  HOST: the product table
+ * and the terms, which are read before the call returns.  One workgroup per proof, one kernel
+ * launch behind one copy of the statement.  gpu backend only.  The call only enqueues on `stream`.
+ * The workspace size needs no backend and is 0 for arguments the call would reject. */
+uint64_t bzamd_check_sumcheck_evaluations_workspace_bytes(unsigned field_id, unsigned num_products,
+                                                          unsigned num_product_terms);
+void bzamd_check_sumcheck_evaluations_device(void* verdicts, unsigned field_id,
+                                             const void* expected_sums, const void* mle_evaluations,
+                                             unsigned num_mles, const void* product_table,
+                                             const unsigned* product_terms, unsigned num_products,
+                                             unsigned num_product_terms, unsigned num_proofs,
+                                             void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* combined = sum_j coefficients[j] * decode(commitments[j]): the a_commit that
+ * bzamd_verify_inner_product_device and sxt_curve25519_verify_inner_product take, from the
+ * compressed commitments bzamd_msm_device(SXT_CURVE_RISTRETTO255, ..) writes and the scalars the
+ * caller gave bzamd_combine_columns* (num_commitments x 32 bytes, unreduced values included).
+ * `combined` is one sxt_ristretto255 of any Z.  An encoding the ristretto decoder rejects
+ * contributes the identity and makes the result 0; otherwise it is 1.
+ * 1 <= num_commitments <= 2^28; NULL pointers abort.  HOST operands, blocking, any backend. */
+int bzamd_combine_commitments(struct sxt_ristretto255* combined,
+                              const struct sxt_ristretto255_compressed* commitments,
+                              const void* coefficients, uint64_t num_commitments);
+/* The device form.  DEVICE pointers on the current HIP device: commitments, coefficients (read in
+ * stream order, never written), combined (one sxt_ristretto255, out), valid (one uint32_t, out: 1,
+ * or 0 when an encoding did not decode -- the same kernels run either way) and workspace (at least
+ * bzamd_combine_commitments_workspace_bytes(num_commitments), 160 bytes a commitment; less aborts;
+ * any alignment).  A decode kernel, one lane per commitment, then one engine call with projective
+ * output (a pending bzamd_pipeline_next is not consumed).  gpu backend only.  The call only
+ * enqueues on `stream`.  The workspace size needs no backend and is 0 outside the limits. */
+uint64_t bzamd_combine_commitments_workspace_bytes(uint64_t num_commitments);
+void bzamd_combine_commitments_device(void* combined, void* valid, const void* commitments,
+                                      const void* coefficients, uint64_t num_commitments,
+                                      void* workspace, uint64_t workspace_bytes, void* stream);
+
 /* The inner-product prover on device-resident vectors: sxt_curve25519_prove_inner_product as a
  * chain of kernels that never returns to the host between rounds.  DEVICE pointers on the current
  * HIP device: l_vector, r_vector (ceil_log2(n) x 32 bytes each; may be NULL for n = 1), ap_value
