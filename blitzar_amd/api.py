@@ -168,6 +168,12 @@ def load():
         lib.bzamd_verify_inner_product_device.argtypes = [vp, vp, u64, u64, vp, vp, vp, vp, vp, vp,
                                                           vp, vp, u64, vp]
         lib.bzamd_verify_inner_product_device.restype = None
+    if hasattr(lib, "bzamd_verify_inner_product_batch_device"):
+        lib.bzamd_inner_product_verify_batch_workspace_bytes.argtypes = [u64, u64]
+        lib.bzamd_inner_product_verify_batch_workspace_bytes.restype = u64
+        lib.bzamd_verify_inner_product_batch_device.argtypes = [vp, vp, u64, u64, u64, vp, vp, vp,
+                                                                vp, vp, vp, vp, vp, u64, vp]
+        lib.bzamd_verify_inner_product_batch_device.restype = None
     lib.bzamd_transcript_init.argtypes = [vp, ctypes.c_char_p, u64]
     lib.bzamd_transcript_init.restype = None
     lib.bzamd_num_devices.restype = ctypes.c_int
@@ -437,6 +443,28 @@ def verify_inner_product_device(n, generators_offset, b_device_ptr, product_devi
                                              b_device_ptr, product_device_ptr, a_commit_device_ptr,
                                              l_device_ptr, r_device_ptr, ap_device_ptr,
                                              workspace_device_ptr, workspace_bytes, stream)
+
+
+def inner_product_verify_batch_workspace_bytes(n, num_proofs):
+    """bytes of device workspace bzamd_verify_inner_product_batch_device needs for num_proofs
+    proofs of n elements (0 outside the limits); needs no backend"""
+    return load().bzamd_inner_product_verify_batch_workspace_bytes(n, num_proofs)
+
+
+def verify_inner_product_batch_device(n, num_proofs, generators_offset, b_device_ptr,
+                                      product_device_ptr, a_commit_device_ptr, l_device_ptr,
+                                      r_device_ptr, ap_device_ptr, transcript_device_ptr,
+                                      verdict_device_ptr, workspace_device_ptr, workspace_bytes,
+                                      generators_device_ptr=None, stream=None):
+    """bzamd_verify_inner_product_batch_device: num_proofs proofs of one length n over one generator
+    set, back to back in every operand (include/blitzar_amd.h has the layout); every operand is a
+    raw device pointer on the current device, the verdicts are num_proofs uint32 there;
+    `generators_device_ptr` None: the built-in generators from `generators_offset`.  Only enqueues
+    on `stream`."""
+    load().bzamd_verify_inner_product_batch_device(
+        verdict_device_ptr, transcript_device_ptr, n, num_proofs, generators_offset,
+        generators_device_ptr, b_device_ptr, product_device_ptr, a_commit_device_ptr, l_device_ptr,
+        r_device_ptr, ap_device_ptr, workspace_device_ptr, workspace_bytes, stream)
 
 
 def verify_inner_product(transcript, n, generators_offset, b_vector, product, a_commit, l_vector,

@@ -1648,6 +1648,44 @@ void bzamd_verify_inner_product_device(void* verdict, void* transcript, uint64_t
       static_cast<hipStream_t>(stream));
 }
 
+uint64_t bzamd_inner_product_verify_batch_workspace_bytes(uint64_t n, uint64_t num_proofs) {
+  return proof::inner_product_verify_batch_workspace_bytes(n, num_proofs);
+}
+
+void bzamd_verify_inner_product_batch_device(void* verdicts, void* transcripts, uint64_t n,
+                                             uint64_t num_proofs, uint64_t generators_offset,
+                                             const void* generators, const void* b_vectors,
+                                             const void* products, const void* a_commits,
+                                             const void* l_vectors, const void* r_vectors,
+                                             const void* ap_values, void* workspace,
+                                             uint64_t workspace_bytes, void* stream) {
+  BZ_RELEASE_ASSERT(verdicts != nullptr, "verdicts must not be null");
+  BZ_RELEASE_ASSERT(transcripts != nullptr, "transcripts must not be null");
+  BZ_RELEASE_ASSERT(ap_values != nullptr, "ap_values must not be null");
+  BZ_RELEASE_ASSERT(products != nullptr, "products must not be null");
+  BZ_RELEASE_ASSERT(a_commits != nullptr, "a_commits must not be null");
+  BZ_RELEASE_ASSERT(b_vectors != nullptr, "b_vectors must not be null");
+  BZ_RELEASE_ASSERT(workspace != nullptr, "workspace must not be null");
+  BZ_RELEASE_ASSERT(n > 0, "b_vectors length must be greater than zero");
+  BZ_RELEASE_ASSERT(num_proofs > 0, "num_proofs must be greater than zero");
+  BZ_RELEASE_ASSERT(n == 1 || (l_vectors != nullptr && r_vectors != nullptr),
+                    "l_vectors and r_vectors must not be null when n is bigger than one");
+  BZ_RELEASE_ASSERT(n <= (uint64_t{1} << 30), "inner products are limited to 2^30 elements");
+  const uint64_t need = proof::inner_product_verify_batch_workspace_bytes(n, num_proofs);
+  BZ_RELEASE_ASSERT(need != 0, "num_proofs x 2^ceil_log2(n) is limited to 2^28");
+  BZ_RELEASE_ASSERT(workspace_bytes >= need,
+                    "the inner-product verifier's workspace is too small");
+  // the current device, the caller's stream and workspace, no lease: as the single form
+  api_state& st = state();
+  BZ_RELEASE_ASSERT(st.backend == SXT_GPU_BACKEND, "device entry points need the GPU backend");
+  proof::verify_inner_product_batch_device(
+      *st.context_for_current_device(), verdicts, transcripts, n, num_proofs, generators_offset,
+      generators, static_cast<const u8*>(b_vectors), static_cast<const u8*>(products), a_commits,
+      static_cast<const u8*>(l_vectors), static_cast<const u8*>(r_vectors),
+      static_cast<const u8*>(ap_values), workspace, workspace_bytes,
+      static_cast<hipStream_t>(stream));
+}
+
 namespace {
 // what the sumcheck entry points share.  `name`: the entry point, for the message
 void check_arguments(const char* name, bool all_present) {

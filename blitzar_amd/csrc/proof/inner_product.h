@@ -39,6 +39,20 @@ void verify_inner_product_device(msm_context& ctx, void* verdict, void* transcri
                                  const u8* r_vector, const u8* ap_value, void* workspace,
                                  u64 workspace_bytes, hipStream_t stream);
 
+// num_proofs proofs of one length over one generator set in one chain
+// (include/blitzar_amd.h: bzamd_verify_inner_product_batch_device): proof i lies at 4 i in
+// `verdicts`, 203 i in `transcripts`, 32 n i in `b_vectors`, 32 i in `products` / `ap_values`,
+// i elements in `a_commits` and 32 ceil_log2(n) i in `l_vectors` / `r_vectors`; the single form is
+// the batch of one.  The size is 0 outside 1 <= n <= 2^30, 1 <= num_proofs, num_proofs np <= 2^28.
+u64 inner_product_verify_batch_workspace_bytes(u64 n, u64 num_proofs);
+void verify_inner_product_batch_device(msm_context& ctx, void* verdicts, void* transcripts, u64 n,
+                                       u64 num_proofs, u64 generators_offset,
+                                       const void* generators, const u8* b_vectors,
+                                       const u8* products, const void* a_commits,
+                                       const u8* l_vectors, const u8* r_vectors,
+                                       const u8* ap_values, void* workspace, u64 workspace_bytes,
+                                       hipStream_t stream);
+
 // services of api/capi.hip the prover needs
 // generators [offset, offset + n) as raw extended coordinates on the host (cache + derivation)
 void host_builtin_generators_unlocked(api_state& st, ed_point* out, u64 n, u64 offset);

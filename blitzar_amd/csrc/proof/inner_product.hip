@@ -528,39 +528,53 @@ void prove_inner_product_device(msm_context& ctx, u8* l_vector, u8* r_vector, u8
 }
 
 //--------------------------------------------------------------------------------------------------
-// the verifier's chain: everything in the caller's workspace as
-//   generators  G = [a_commit | Q | g_0 .. g_{np-1} | L_0 .. | R_0 ..]
-//   scalars     S = [1 | product | e_Q | e_0 .. e_{np-1} | -x_i^2 .. | -x_i^-2 ..]
-// so that ONE call of the MSM engine with two columns yields
-//   rows S[2 ..] over G[1 ..]  = the commitment the proof's scalars stand for,
-//   rows S[0 .. 2] over G[0 ..] = a_commit + product Q,
-// and the proof is accepted when the two encodings are equal and every L and R decoded.
+// the verifier's chain, for num_proofs proofs of one length over ONE
+// generator set: everything in the caller's workspace as
+//   generators  G = [Q | g_0 .. g_{np-1} | (a_commit_i | L_i,0 .. | R_i,0 ..) for i < num_proofs]
+//   shared column i   [e_Q,i - product_i | e_i,0 .. e_i,np-1]   at generator offset 0
+//   own column i      [1 | x_i,j^2 .. | x_i,j^-2 ..]            at offset np + 1 + i (1 + 2 rounds)
+// so that ONE call of the MSM engine with 2 num_proofs columns yields both sides of
+//   (e_Q - product) Q + <e, g>  ==  a_commit + sum_j x_j^2 L_j + x_j^-2 R_j,
+// the reference's equation with the per-proof terms moved to the right: the big part of G is
+// shared by every proof.  Proof i is accepted when its two encodings are equal and every one of its
+// L and R decoded.  The single form is the batch of one.
 //--------------------------------------------------------------------------------------------------
 namespace {
 constexpr u32 kMaxRounds = 30; // n <= 2^30
+constexpr u32 kMaxProofPartials = 1024; // workgroups of k_verify_expand per proof, at most
 
-// what the challenge kernel leaves for the expansion, and the decode kernel for the verdict
+// what the challenge kernel leaves for the expansion, and the decode kernel for the verdict; one
+// per proof
 struct verify_slot {
   s25::fe seed;             // ap prod x_i^-1, plain
   s25::fe x_sq[kMaxRounds]; // Montgomery form
   u32 undecodable[2 * kMaxRounds];
 };
 
-constexpr u64 kVerifyRowProduct = 1, kVerifyRowQ = 2, kVerifyRowG = 3;
-
-// One wavefront: the whole transcript of the proof (init, a challenge per round, stored back), then
-// lane i < rounds turns x_i into the rows -x_i^2 and -x_i^-2 and x_sq[i]; lane 0 multiplies the
-// inverses up into the seed.  Column B's rows [1, product] and a_commit's place in G are filled
-// here as well.  rounds = 0 (n = 1): the exponents are b_0 ap on Q and ap on g_0.
+// One wavefront per proof (blockIdx.x): the whole transcript of the proof (init, a challenge per
+// round, stored back), then lane j < rounds turns x_j into the own column's rows x_j^2 and x_j^-2
+// and x_sq[j]; lane 0 multiplies the inverses up into the seed.  The own column's row [1] and
+// a_commit's place in G are filled here as well.  rounds = 0 (n = 1): the shared column is
+// [b_0 ap - product | ap].  Every operand is read bytewise: the proofs lie back to back.
 __global__ void __launch_bounds__(64)
-    k_verify_challenges(u8* __restrict__ s, verify_slot* __restrict__ slot,
-                        ed_point* __restrict__ g, u8* transcript, const u8* __restrict__ l_vector,
-                        const u8* __restrict__ r_vector, const u8* __restrict__ ap_value,
-                        const u8* __restrict__ product, const u8* __restrict__ b_vector,
-                        const ed_point* __restrict__ a_commit, u64 n, u32 rounds) {
+    k_verify_challenges(u8* __restrict__ shared_rows, u8* __restrict__ own_rows,
+                        verify_slot* __restrict__ slots, ed_point* __restrict__ g_own,
+                        u8* transcripts, const u8* __restrict__ l_vectors,
+                        const u8* __restrict__ r_vectors, const u8* __restrict__ ap_values,
+                        const u8* __restrict__ products, const u8* __restrict__ b_vectors,
+                        const u8* __restrict__ a_commits, u64 n, u32 rounds) {
   __shared__ wave_state w;
   __shared__ s25::fe inverses[kMaxRounds];
   const u32 lane = threadIdx.x;
+  const u64 proof = blockIdx.x;
+  const u64 np = u64{1} << rounds;
+  u8* transcript = transcripts + sizeof(transcript_state) * proof;
+  const u8* l_vector = l_vectors + 32 * rounds * proof;
+  const u8* r_vector = r_vectors + 32 * rounds * proof;
+  verify_slot* slot = slots + proof;
+  u8* own = own_rows + 32 * (1 + 2 * u64{rounds}) * proof;
+  u8* shared = shared_rows + 32 * (np + 1) * proof;
+
   wave_load_transcript(w.t, transcript);
   init_transcript<wave_sponge>(&w.t, n);
   s25::fe mine = s25::F::zero();
@@ -575,26 +589,27 @@ __global__ void __launch_bounds__(64)
   }
   wave_store_transcript(transcript, w.t);
 
-  if (lane < 32) {
-    s[lane] = lane == 0 ? 1 : 0;
-    s[32 * kVerifyRowProduct + lane] = product[lane];
+  if (lane < 32) own[lane] = lane == 0 ? 1 : 0;
+  {
+    u8* to = reinterpret_cast<u8*>(g_own + (1 + 2 * u64{rounds}) * proof);
+    const u8* from = a_commits + sizeof(ed_point) * proof;
+    for (u32 i = lane; i < sizeof(ed_point); i += 64) to[i] = from[i];
   }
-  if (lane == 0) g[0] = *a_commit;
-  const s25::fe ap = s25::load(ap_value);
-  const u64 np = u64{1} << rounds;
+  const s25::fe ap = s25::load(ap_values + 32 * proof);
   if (rounds == 0) {
     if (lane == 0) {
-      s25::store(s + 32 * kVerifyRowQ, s25::F::mul(s25::to_mont(s25::load(b_vector)), ap));
-      s25::store(s + 32 * kVerifyRowG, s25::from_mont(s25::to_mont(ap)));
+      const s25::fe product = s25::from_mont(s25::to_mont(s25::load(products + 32 * proof)));
+      const s25::fe e_q = s25::F::mul(s25::to_mont(s25::load(b_vectors + 32 * proof)), ap);
+      s25::store(shared, s25::add(e_q, s25::neg(product)));
+      s25::store(shared + 32, s25::from_mont(s25::to_mont(ap)));
     }
     return;
   }
   if (lane < rounds) {
     const s25::fe x_inv = s25::F::invert(mine); // zero for zero, as scalar::inverse
     const s25::fe x_sq = s25::F::mul(mine, mine);
-    s25::store(s + 32 * (kVerifyRowG + np + lane), s25::from_mont(s25::neg(x_sq)));
-    s25::store(s + 32 * (kVerifyRowG + np + rounds + lane),
-               s25::from_mont(s25::neg(s25::F::mul(x_inv, x_inv))));
+    s25::store(own + 32 * (1 + lane), s25::from_mont(x_sq));
+    s25::store(own + 32 * (1 + rounds + lane), s25::from_mont(s25::F::mul(x_inv, x_inv)));
     slot->x_sq[lane] = x_sq;
     inverses[lane] = x_inv;
   }
@@ -606,150 +621,261 @@ __global__ void __launch_bounds__(64)
   }
 }
 
-// One lane per L / R point: G[first + i] = the decoded point, or the identity and a raised flag
-// for an encoding ristretto::decode rejects -- the chain runs on whatever the proof holds
-__global__ void __launch_bounds__(64)
-    k_verify_decode(ed_point* __restrict__ g, verify_slot* __restrict__ slot,
-                    const u8* __restrict__ l_vector, const u8* __restrict__ r_vector, u32 rounds) {
-  const u32 i = threadIdx.x;
-  if (i >= 2 * rounds) return;
-  const u8* bytes = i < rounds ? l_vector + 32 * i : r_vector + 32 * (i - rounds);
+// One lane per L / R point of the batch, 2 rounds of them per proof: its place in G = the decoded
+// point, or the identity and a raised flag for an encoding ristretto::decode rejects -- the chain
+// runs on whatever the proofs hold
+__global__ void __launch_bounds__(256)
+    k_verify_decode(ed_point* __restrict__ g_own, verify_slot* __restrict__ slots,
+                    const u8* __restrict__ l_vectors, const u8* __restrict__ r_vectors, u32 rounds,
+                    u32 num_proofs) {
+  const u64 at = static_cast<u64>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (at >= 2 * u64{rounds} * num_proofs) return;
+  const u64 proof = at / (2 * rounds);
+  const u32 i = static_cast<u32>(at % (2 * rounds));
+  const u8* bytes = i < rounds ? l_vectors + 32 * (rounds * proof + i)
+                               : r_vectors + 32 * (rounds * proof + (i - rounds));
   ed_point p;
   const bool ok = ristretto29::decode(p, bytes);
-  g[i] = ok ? p : ed::identity();
-  slot->undecodable[i] = ok ? 0 : 1;
+  g_own[(1 + 2 * u64{rounds}) * proof + 1 + i] = ok ? p : ed::identity();
+  slots[proof].undecodable[i] = ok ? 0 : 1;
 }
 
-// the caller's np + 1 generators, the last one Q, into [Q | g_0 .. g_{np-1}]
+// the caller's np + 1 generators, the last one Q, into [Q | g_0 .. g_{np-1}]; by words where the
+// caller's pointer allows it
 __global__ void __launch_bounds__(256)
-    k_verify_generators(ed_point* __restrict__ g, const ed_point* __restrict__ generators, u32 np) {
+    k_verify_generators(ed_point* __restrict__ g, const u8* __restrict__ generators, u32 np) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i > np) return;
-  g[i == np ? 0 : i + 1] = generators[i];
-}
-
-// b into the workspace where the caller's pointer is not 8-byte aligned (as k_load reads it)
-__global__ void __launch_bounds__(256)
-    k_verify_copy_b(u64* __restrict__ out, const u8* __restrict__ b, u32 n) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  for (int k = 0; k < 4; ++k) {
-    const u64 at = 32 * static_cast<u64>(i) + 8 * k;
-    u64 v = 0;
-    for (int j = 7; j >= 0; --j) v = (v << 8) | b[at + j];
-    out[4 * static_cast<u64>(i) + k] = v;
+  const u8* from = generators + sizeof(ed_point) * static_cast<u64>(i);
+  ed_point* to = g + (i == np ? 0 : i + 1);
+  if ((reinterpret_cast<uintptr_t>(generators) & 7) == 0) {
+    *to = *reinterpret_cast<const ed_point*>(from);
+  } else {
+    u8* bytes = reinterpret_cast<u8*>(to);
+    for (u32 k = 0; k < sizeof(ed_point); ++k) bytes[k] = from[k];
   }
 }
 
-// e_i = seed prod_{j : bit j of i set} x_sq[rounds - 1 - j], i < np: the closed form of the
-// reference's doubling loop (verification_computation.cc:77-91); canonical rows
+// The expansion fused with <e, b>:
+//   e_k = seed prod_{j : bit j of k set} x_sq[rounds - 1 - j],  k < np,
+// the closed form of the reference's doubling loop (verification_computation.cc:77-91).  A lane
+// writes the canonical row of its e_k into the proof's shared column and, for k < n, multiplies it
+// by b_k while it holds it; the workgroup adds the products up (LDS tree) into one partial.
+//
+// (proof, k) to lanes, rounds >= 1:
+//   np >= 256: a proof has `partials` = np / (256 items) workgroups, items = max(1, np / 2^18), so
+//     that no proof has more than kMaxProofPartials partials; workgroup blockIdx.x works for proof
+//     blockIdx.x / partials on the rows [(chunk items + t) 256 + lane, t < items): coalesced.
+//   np < 256: the flat index proof np + k is cut into workgroups, 256 / np whole proofs each, so
+//     that a batch of short proofs fills its workgroups; the tree stops at the proof's np lanes.
+// b is read by words where the caller's pointer is 8-byte aligned (32 n i keeps that), bytewise
+// otherwise.
 __global__ void __launch_bounds__(256)
-    k_verify_expand(u64* __restrict__ e, const verify_slot* __restrict__ slot, u32 rounds, u32 np) {
-  __shared__ s25::fe x_sq[kMaxRounds];
-  if (threadIdx.x < rounds) x_sq[threadIdx.x] = slot->x_sq[threadIdx.x];
+    k_verify_expand(u8* __restrict__ shared_rows, s25::fe* __restrict__ partials,
+                    const verify_slot* __restrict__ slots, const u8* __restrict__ b_vectors, u32 n,
+                    u32 rounds, u32 items, u32 proof_partials, u32 num_proofs) {
+  __shared__ s25::fe x_sq[128]; // np < 256: (256 >> rounds) rounds <= 128; else rounds <= 30
+  __shared__ s25::fe tree[256];
+  const u32 np = 1u << rounds;
+  const u32 lanes = np < 256 ? np : 256; // of one proof in this workgroup
+  const u32 proofs_here = 256 / lanes;
+  const u32 local = threadIdx.x / lanes;
+  u32 first, chunk;
+  if (np < 256) {
+    first = blockIdx.x * proofs_here;
+    chunk = 0;
+  } else {
+    first = blockIdx.x / proof_partials;
+    chunk = blockIdx.x % proof_partials;
+  }
+  if (threadIdx.x < proofs_here * rounds) {
+    const u32 p = first + threadIdx.x / rounds;
+    if (p < num_proofs) x_sq[threadIdx.x] = slots[p].x_sq[threadIdx.x % rounds];
+  }
   __syncthreads();
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= np) return;
-  s25::fe acc = slot->seed;
-  for (u32 j = 0; j < rounds; ++j) {
-    if ((i >> j) & 1) acc = s25::F::mul(x_sq[rounds - 1 - j], acc);
+  const u32 proof = first + local;
+  s25::fe sum = s25::F::zero();
+  if (proof < num_proofs) {
+    const s25::fe seed = slots[proof].seed;
+    const s25::fe* mine = x_sq + local * rounds;
+    u64* rows = reinterpret_cast<u64*>(shared_rows + 32 * (static_cast<u64>(np) + 1) * proof + 32);
+    const u8* b = b_vectors + 32 * static_cast<u64>(n) * proof;
+    const bool aligned = (reinterpret_cast<uintptr_t>(b_vectors) & 7) == 0;
+    for (u32 t = 0; t < items; ++t) {
+      const u32 k = (chunk * items + t) * 256 + (threadIdx.x & (lanes - 1));
+      s25::fe e = seed;
+      for (u32 j = 0; j < rounds; ++j) {
+        if ((k >> j) & 1) e = s25::F::mul(mine[rounds - 1 - j], e);
+      }
+      u64 words[4];
+      s25::store_words(words, e);
+      for (int q = 0; q < 4; ++q) rows[4 * static_cast<u64>(k) + q] = words[q];
+      if (k < n) {
+        const u8* at = b + 32 * static_cast<u64>(k);
+        const s25::fe b_k =
+            aligned ? s25::load_words(reinterpret_cast<const u64*>(at)) : s25::load(at);
+        sum = s25::add(sum, s25::F::mul(e, b_k));
+      }
+    }
   }
-  u64 w[4];
-  s25::store_words(w, acc);
-  for (int k = 0; k < 4; ++k) e[4 * static_cast<u64>(i) + k] = w[k];
+  tree[threadIdx.x] = sum;
+  __syncthreads();
+  for (u32 stride = lanes / 2; stride > 0; stride >>= 1) {
+    if ((threadIdx.x & (lanes - 1)) < stride) {
+      tree[threadIdx.x] = s25::add(tree[threadIdx.x], tree[threadIdx.x + stride]);
+    }
+    __syncthreads();
+  }
+  if ((threadIdx.x & (lanes - 1)) == 0 && proof < num_proofs) {
+    partials[static_cast<u64>(proof) * proof_partials + chunk] = tree[threadIdx.x];
+  }
 }
 
-// One wavefront: accepted when the engine's two encodings are equal and no point failed to decode
+// One wavefront per proof: e_Q - product (canonical) from the proof's partials (sums of e_k b_k / R)
+// into row 0 of its shared column
 __global__ void __launch_bounds__(64)
-    k_verify_verdict(u32* __restrict__ verdict, const u8* __restrict__ encodings,
-                     const verify_slot* __restrict__ slot, u32 rounds) {
-  const u32 lane = threadIdx.x;
-  bool ok = true;
-  if (lane < 32) ok = encodings[lane] == encodings[32 + lane];
-  if (lane < 2 * rounds) ok = ok && slot->undecodable[lane] == 0;
-  const bool all = __all(ok) != 0;
-  if (lane == 0) *verdict = all ? 1 : 0;
+    k_verify_finish(u8* __restrict__ shared_rows, const s25::fe* __restrict__ partials,
+                    const u8* __restrict__ products, u32 proof_partials, u32 np) {
+  __shared__ s25::fe tree[64];
+  const u64 proof = blockIdx.x;
+  s25::fe sum = s25::F::zero();
+  for (u32 t = threadIdx.x; t < proof_partials; t += 64) {
+    sum = s25::add(sum, partials[proof * proof_partials + t]);
+  }
+  tree[threadIdx.x] = sum;
+  __syncthreads();
+  for (u32 stride = 32; stride > 0; stride >>= 1) {
+    if (threadIdx.x < stride) {
+      tree[threadIdx.x] = s25::add(tree[threadIdx.x], tree[threadIdx.x + stride]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const s25::fe product = s25::from_mont(s25::to_mont(s25::load(products + 32 * proof)));
+    const s25::fe e_q = s25::F::mul(tree[0], s25::r2());
+    s25::store(shared_rows + 32 * (static_cast<u64>(np) + 1) * proof,
+               s25::add(e_q, s25::neg(product)));
+  }
 }
 
-// the caller's workspace of the verifier, for np = 2^rounds
-struct verify_layout {
-  size_t generators, scalars, b, partials, slot, encodings, total;
-  verify_layout(u64 np, u64 rounds) {
+// One wavefront per proof, four to a workgroup: accepted when the engine's two encodings of the
+// proof are equal and none of its points failed to decode.  The word is stored bytewise: verdicts
+// need no alignment.
+__global__ void __launch_bounds__(256)
+    k_verify_verdict(u8* __restrict__ verdicts, const u8* __restrict__ encodings,
+                     const verify_slot* __restrict__ slots, u32 rounds, u32 num_proofs) {
+  const u32 lane = threadIdx.x & 63;
+  const u32 proof = blockIdx.x * 4 + threadIdx.x / 64;
+  if (proof >= num_proofs) return; // the whole wavefront
+  bool ok = true;
+  if (lane < 32) {
+    ok = encodings[32 * static_cast<u64>(proof) + lane] ==
+         encodings[32 * (static_cast<u64>(num_proofs) + proof) + lane];
+  }
+  if (lane < 2 * rounds) ok = ok && slots[proof].undecodable[lane] == 0;
+  const bool all = __all(ok) != 0;
+  if (lane < 4) verdicts[4 * static_cast<u64>(proof) + lane] = lane == 0 && all ? 1 : 0;
+}
+
+// the caller's workspace of the batch verifier, for np = 2^rounds
+struct verify_batch_layout {
+  size_t generators, shared_rows, own_rows, partials, slots, encodings, total;
+  u32 items, proof_partials; // k_verify_expand's geometry
+  verify_batch_layout(u64 np, u64 rounds, u64 num_proofs) {
+    items = static_cast<u32>(std::max<u64>(1, np / (256 * u64{kMaxProofPartials})));
+    proof_partials = np < 256 ? 1 : static_cast<u32>(np / (256 * u64{items}));
     workspace_carver carve;
-    generators = carve.take(sizeof(ed_point) * (2 + np + 2 * rounds));
-    scalars = carve.take(32 * (kVerifyRowG + np + 2 * rounds));
-    b = carve.take(32 * np);
-    partials = carve.take(sizeof(s25::fe) * kPartialBlocks);
-    slot = carve.take(sizeof(verify_slot));
-    encodings = carve.take(64);
+    generators = carve.take(sizeof(ed_point) * (np + 1 + num_proofs * (1 + 2 * rounds)));
+    shared_rows = carve.take(32 * (np + 1) * num_proofs);
+    own_rows = carve.take(32 * (1 + 2 * rounds) * num_proofs);
+    partials = carve.take(sizeof(s25::fe) * proof_partials * num_proofs);
+    slots = carve.take(sizeof(verify_slot) * num_proofs);
+    encodings = carve.take(64 * num_proofs);
     total = carve.total();
   }
 };
 
-void enqueue_verify_chain(msm_context& ctx, u32* verdict, u8* transcript, u64 n,
-                          u64 generators_offset, const ed_point* generators, const u8* b_vector,
-                          const u8* product, const ed_point* a_commit, const u8* l_vector,
-                          const u8* r_vector, const u8* ap_value, void* workspace,
+// the single form's workspace, as it was before it became the batch of one (a b copy beside the
+// exponents); the batch of one fits into it at every np, which the chain asserts
+struct verify_layout {
+  size_t total;
+  verify_layout(u64 np, u64 rounds) {
+    workspace_carver carve;
+    carve.take(sizeof(ed_point) * (2 + np + 2 * rounds));
+    carve.take(32 * (3 + np + 2 * rounds));
+    carve.take(32 * np);
+    carve.take(sizeof(s25::fe) * kPartialBlocks);
+    carve.take(sizeof(verify_slot));
+    carve.take(64);
+    total = carve.total();
+  }
+};
+
+bool verify_batch_in_limits(u64 n, u64 num_proofs) {
+  if (n == 0 || n > (u64{1} << 30) || num_proofs == 0 || num_proofs > (u64{1} << 28)) return false;
+  return num_proofs * (u64{1} << ceil_log2(n)) <= (u64{1} << 28);
+}
+
+void enqueue_verify_chain(msm_context& ctx, u8* verdicts, u8* transcripts, u64 n, u64 num_proofs,
+                          u64 generators_offset, const u8* generators, const u8* b_vectors,
+                          const u8* products, const u8* a_commits, const u8* l_vectors,
+                          const u8* r_vectors, const u8* ap_values, void* workspace,
                           u64 workspace_bytes, hipStream_t stream) {
   const u64 rounds = ceil_log2(n), np = u64{1} << rounds;
-  const verify_layout layout{np, rounds};
+  const verify_batch_layout layout{np, rounds, num_proofs};
   BZ_RELEASE_ASSERT(workspace != nullptr && workspace_bytes >= layout.total,
                     "the inner-product verifier's workspace is too small");
   u8* base = workspace_carver::aligned(workspace);
   ed_point* d_g = reinterpret_cast<ed_point*>(base + layout.generators);
-  u8* d_s = base + layout.scalars;
-  u64* d_e = reinterpret_cast<u64*>(d_s + 32 * kVerifyRowG);
-  u64* d_b = reinterpret_cast<u64*>(base + layout.b);
+  ed_point* d_g_own = d_g + np + 1;
+  u8* d_shared = base + layout.shared_rows;
+  u8* d_own = base + layout.own_rows;
   auto* d_partials = reinterpret_cast<s25::fe*>(base + layout.partials);
-  auto* d_slot = reinterpret_cast<verify_slot*>(base + layout.slot);
+  auto* d_slots = reinterpret_cast<verify_slot*>(base + layout.slots);
   u8* d_encodings = base + layout.encodings;
-  const u32 blocks = static_cast<u32>((np + 255) / 256);
+  const u32 proofs = static_cast<u32>(num_proofs), r = static_cast<u32>(rounds);
+  const u64 own_rows = 1 + 2 * rounds;
 
-  // G: nothing here depends on the challenges
+  // G: nothing here depends on the challenges, and [Q | g] is written once for the batch
   if (generators == nullptr) {
-    builtin_generators_enqueue(d_g + 1, generators_offset + np, 1, stream);
-    builtin_generators_enqueue(d_g + 2, generators_offset, np, stream);
+    builtin_generators_enqueue(d_g, generators_offset + np, 1, stream);
+    builtin_generators_enqueue(d_g + 1, generators_offset, np, stream);
     g_kernel_launches += 2;
   } else {
     hipLaunchKernelGGL(k_verify_generators, dim3(static_cast<u32>((np + 256) / 256)), dim3(256), 0,
-                       stream, d_g + 1, generators, static_cast<u32>(np));
+                       stream, d_g, generators, static_cast<u32>(np));
     g_kernel_launches += 1;
   }
   if (rounds != 0) {
-    hipLaunchKernelGGL(k_verify_decode, dim3(1), dim3(64), 0, stream, d_g + 2 + np, d_slot, l_vector,
-                       r_vector, static_cast<u32>(rounds));
+    hipLaunchKernelGGL(k_verify_decode, dim3(static_cast<u32>((2 * rounds * num_proofs + 255) / 256)),
+                       dim3(256), 0, stream, d_g_own, d_slots, l_vectors, r_vectors, r, proofs);
     g_kernel_launches += 1;
   }
-  hipLaunchKernelGGL(k_verify_challenges, dim3(1), dim3(64), 0, stream, d_s, d_slot, d_g, transcript,
-                     l_vector, r_vector, ap_value, product, b_vector, a_commit, n,
-                     static_cast<u32>(rounds));
+  hipLaunchKernelGGL(k_verify_challenges, dim3(proofs), dim3(64), 0, stream, d_shared, d_own,
+                     d_slots, d_g_own, transcripts, l_vectors, r_vectors, ap_values, products,
+                     b_vectors, a_commits, n, r);
   g_kernel_launches += 1;
   if (rounds != 0) {
-    hipLaunchKernelGGL(k_verify_expand, dim3(blocks), dim3(256), 0, stream, d_e, d_slot,
-                       static_cast<u32>(rounds), static_cast<u32>(np));
-    // e_Q = <e, b> over the n entries of b
-    const u64* b_words = reinterpret_cast<const u64*>(b_vector);
-    if ((reinterpret_cast<uintptr_t>(b_vector) & 7) != 0) {
-      hipLaunchKernelGGL(k_verify_copy_b, dim3(static_cast<u32>((n + 255) / 256)), dim3(256), 0,
-                         stream, d_b, b_vector, static_cast<u32>(n));
-      g_kernel_launches += 1;
-      b_words = d_b;
-    }
-    const u32 partial_blocks = std::min(kPartialBlocks, static_cast<u32>((n + 255) / 256));
-    hipLaunchKernelGGL(k_inner_product, dim3(partial_blocks), dim3(256), 0, stream, d_partials, d_e,
-                       b_words, static_cast<u32>(n));
-    hipLaunchKernelGGL(k_cross_finish, dim3(1), dim3(kPartialBlocks), 0, stream,
-                       reinterpret_cast<u64*>(d_s + 32 * kVerifyRowQ), static_cast<u64*>(nullptr),
-                       d_partials, partial_blocks);
-    g_kernel_launches += 3;
+    const u64 blocks = np < 256 ? (num_proofs * np + 255) / 256 : num_proofs * layout.proof_partials;
+    hipLaunchKernelGGL(k_verify_expand, dim3(static_cast<u32>(blocks)), dim3(256), 0, stream,
+                       d_shared, d_partials, d_slots, b_vectors, static_cast<u32>(n), r, layout.items,
+                       layout.proof_partials, proofs);
+    hipLaunchKernelGGL(k_verify_finish, dim3(proofs), dim3(64), 0, stream, d_shared, d_partials,
+                       products, layout.proof_partials, static_cast<u32>(np));
+    g_kernel_launches += 2;
   }
   BZ_HIP_CHECK(hipGetLastError());
-  host_column col_a = byte_column(d_s + 32 * kVerifyRowQ, 1 + np + 2 * rounds, 32, false);
-  col_a.generator_offset = 1;
-  const host_column col_b = byte_column(d_s, 2, 32, false);
-  curve25519_vtable().msm(ctx, d_encodings, 32, false, {col_a, col_b}, nullptr, d_g, stream, false);
-  hipLaunchKernelGGL(k_verify_verdict, dim3(1), dim3(64), 0, stream, verdict, d_encodings, d_slot,
-                     static_cast<u32>(rounds));
+  // shared columns first, then own columns: encodings[i] against encodings[num_proofs + i].  The
+  // engine cuts a call into batches of its own where the columns exceed a launch grid.
+  std::vector<host_column> cols(2 * num_proofs);
+  for (u64 i = 0; i < num_proofs; ++i) {
+    cols[i] = byte_column(d_shared + 32 * (np + 1) * i, np + 1, 32, false);
+    cols[num_proofs + i] = byte_column(d_own + 32 * own_rows * i, own_rows, 32, false);
+    cols[num_proofs + i].generator_offset = np + 1 + own_rows * i;
+  }
+  curve25519_vtable().msm(ctx, d_encodings, 32, false, cols, nullptr, d_g, stream, false);
+  hipLaunchKernelGGL(k_verify_verdict, dim3((proofs + 3) / 4), dim3(256), 0, stream, verdicts,
+                     d_encodings, d_slots, r, proofs);
   BZ_HIP_CHECK(hipGetLastError());
   g_kernel_launches += 1;
 }
@@ -762,15 +888,40 @@ u64 inner_product_verify_workspace_bytes(u64 n) {
   return verify_layout{u64{1} << rounds, rounds}.total;
 }
 
+u64 inner_product_verify_batch_workspace_bytes(u64 n, u64 num_proofs) {
+  if (!verify_batch_in_limits(n, num_proofs)) return 0;
+  const u64 rounds = ceil_log2(n);
+  return verify_batch_layout{u64{1} << rounds, rounds, num_proofs}.total;
+}
+
 void verify_inner_product_device(msm_context& ctx, void* verdict, void* transcript, u64 n,
                                  u64 generators_offset, const void* generators, const u8* b_vector,
                                  const u8* product, const void* a_commit, const u8* l_vector,
                                  const u8* r_vector, const u8* ap_value, void* workspace,
                                  u64 workspace_bytes, hipStream_t stream) {
-  enqueue_verify_chain(ctx, static_cast<u32*>(verdict), static_cast<u8*>(transcript), n,
-                       generators_offset, static_cast<const ed_point*>(generators), b_vector,
-                       product, static_cast<const ed_point*>(a_commit), l_vector, r_vector, ap_value,
-                       workspace, workspace_bytes, stream);
+  // the batch of one, in the workspace this entry point has always asked for
+  BZ_RELEASE_ASSERT(workspace != nullptr &&
+                        workspace_bytes >= inner_product_verify_workspace_bytes(n),
+                    "the inner-product verifier's workspace is too small");
+  enqueue_verify_chain(ctx, static_cast<u8*>(verdict), static_cast<u8*>(transcript), n, 1,
+                       generators_offset, static_cast<const u8*>(generators), b_vector, product,
+                       static_cast<const u8*>(a_commit), l_vector, r_vector, ap_value, workspace,
+                       workspace_bytes, stream);
+}
+
+void verify_inner_product_batch_device(msm_context& ctx, void* verdicts, void* transcripts, u64 n,
+                                       u64 num_proofs, u64 generators_offset,
+                                       const void* generators, const u8* b_vectors,
+                                       const u8* products, const void* a_commits,
+                                       const u8* l_vectors, const u8* r_vectors,
+                                       const u8* ap_values, void* workspace, u64 workspace_bytes,
+                                       hipStream_t stream) {
+  BZ_RELEASE_ASSERT(verify_batch_in_limits(n, num_proofs),
+                    "1 <= n <= 2^30, 1 <= num_proofs and num_proofs x np <= 2^28");
+  enqueue_verify_chain(ctx, static_cast<u8*>(verdicts), static_cast<u8*>(transcripts), n, num_proofs,
+                       generators_offset, static_cast<const u8*>(generators), b_vectors, products,
+                       static_cast<const u8*>(a_commits), l_vectors, r_vectors, ap_values, workspace,
+                       workspace_bytes, stream);
 }
 
 bool verify_inner_product(api_state& st, void* transcript_bytes, u64 n, u64 generators_offset,

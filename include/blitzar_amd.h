@@ -544,6 +544,56 @@ void bzamd_verify_inner_product_device(void* verdict, void* transcript, uint64_t
                                        const void* r_vector, const void* ap_value,
                                        void* workspace, uint64_t workspace_bytes, void* stream);
 
+/* num_proofs independent inner-product proofs of ONE length n over ONE generator set, verified in
+ * one chain of kernels whose launch count outside the MSM engine does not depend on num_proofs:
+ * the generators (NULL: the built-in ones from generators_offset; otherwise np + 1 resident
+ * sxt_ristretto255 elements, the last one Q) are derived or copied once for the batch, and one
+ * engine call takes two columns per proof.  With rounds = ceil_log2(n) and np = 2^rounds, every
+ * pointer is DEVICE memory on the current HIP device, the proofs lie back to back at byte
+ * granularity, and no pointer needs any alignment.  Proof i:
+ *
+ *   operand               offset          size                          access
+ *   verdicts              4 i             one uint32_t                  out
+ *   transcripts           203 i           203 bytes                     in / out, used in place
+ *   b_vectors             32 n i          n x 32 bytes (n, not np)      read
+ *   products              32 i            32 bytes                      read
+ *   ap_values             32 i            32 bytes                      read
+ *   a_commits             i elements      one sxt_ristretto255, any Z   read
+ *   l_vectors, r_vectors  32 rounds i     rounds x 32 bytes each        read
+ *
+ * (l_vectors and r_vectors may be NULL for n = 1).  This is where bzamd_prove_inner_product_device
+ * leaves a proof when it is handed the matching offsets.
+ *
+ * Proof i is exactly bzamd_verify_inner_product_device, and therefore
+ * sxt_curve25519_verify_inner_product, on the same bytes: the same verdict and the same 203 bytes
+ * of transcript afterwards; unreduced b, product and ap are taken as given; an L or R that does not
+ * decode gives verdict 0 for that proof only, and what is launched never depends on any proof's
+ * contents.  Proofs do not influence each other, and no input is written.  The chain compares
+ *   (e_Q - product) Q + <e, g>   with   a_commit + sum_j x_j^2 L_j + x_j^-2 R_j,
+ * the reference's equation with the per-proof points moved to one side so that [Q | g] is shared;
+ * the two sides have equal ristretto encodings exactly when the reference's have, provided a_commit
+ * is a ristretto element (a point of the even subgroup, as every decoded or computed commitment
+ * is) -- which the single form assumes as well.
+ *
+ * gpu backend only.  The call only enqueues on `stream`: no synchronise, no callback, no allocation
+ * but the MSM engine's own grow-only buffers (the engine cuts a call of more columns than a launch
+ * grid takes into batches of its own); a pending bzamd_pipeline_next is not consumed; a later call
+ * on the same stream may use the same workspace.
+ *
+ * Limits: 1 <= n <= 2^30, num_proofs >= 1, num_proofs x np <= 2^28.  Aborts before anything is
+ * launched: a NULL pointer (except generators, and l_vectors / r_vectors at n = 1), n or
+ * num_proofs outside the limits, a workspace smaller than
+ * bzamd_inner_product_verify_batch_workspace_bytes(n, num_proofs), which needs no backend, depends
+ * on n through np alone and returns 0 outside the limits. */
+uint64_t bzamd_inner_product_verify_batch_workspace_bytes(uint64_t n, uint64_t num_proofs);
+void bzamd_verify_inner_product_batch_device(void* verdicts, void* transcripts, uint64_t n,
+                                             uint64_t num_proofs, uint64_t generators_offset,
+                                             const void* generators, const void* b_vectors,
+                                             const void* products, const void* a_commits,
+                                             const void* l_vectors, const void* r_vectors,
+                                             const void* ap_values, void* workspace,
+                                             uint64_t workspace_bytes, void* stream);
+
 /* From the sumcheck's outputs to the inner-product argument's inputs: the two vectors with which
  * one inner-product proof opens every claimed evaluation mle_evaluations[j] = f_j(r).  Both are
  * exact field arithmetic; elements are 32 bytes in the representation sxt_prove_sumcheck takes for

@@ -5,6 +5,9 @@ looped over a batch that lies in HBM, and bzamd_combine_commitments_device.
 
     python tools/verifier_bench.py [--batches 1,256,4096] [--variables 20] [--degree 3]
                                    [--commitments 8,1024] [--samples 15] [--out FILE]
+                                   [--parent-lib <libblitzar_amd.so of the parent commit>]
+                                   [--inner-product 1024:1,16,256/65536:1,16,64]
+                                   [--legs sumcheck,combine,inner_product]
 
 Legs, per field and batch B (proofs of --variables variables at round degree --degree; one accepted
 proof repeated B times: the work of a proof does not depend on its bytes, only on being accepted to
@@ -17,6 +20,15 @@ the last round):
   check_device   one bzamd_check_sumcheck_evaluations_device call.
 A and B alternate, sample by sample.  Then, per count K of --commitments:
   combine_device bzamd_combine_commitments_device over K commitments the library made itself.
+With --parent-lib, per n and batch B of --inner-product (one accepted proof of n elements, made by
+this build, repeated B times in the batch layout; built-in generators from offset 0):
+  ip_single_loop_parent  (A) bzamd_verify_inner_product_device of --parent-lib (BLITZAR_AMD_LIB
+                 selects it, as in tools/inner_product_bench.py) enqueued B times on one stream with
+                 one workspace, in a child process of its own;
+  ip_batch_device        (B) one bzamd_verify_inner_product_batch_device call of this build, in a
+                 second child process.
+Both children take their samples by the same protocol, in turn; both must accept the intact batch
+and reject exactly the tampered proof of a batch with one tampered ap.
 A sample is the time between two device events around the leg and a synchronise, after two untimed
 runs of every leg; printed per leg, one JSON line (appended to --out, default
 profiles/verifier_bench.jsonl): median, min and max in microseconds.  No figure here is an
@@ -26,7 +38,9 @@ import ctypes
 import json
 import os
 import statistics
+import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
@@ -179,6 +193,133 @@ class Combination:
             self.workspace_bytes, stream=stream.cuda_stream)
 
 
+class InnerProductBatch:
+    """B copies of one inner-product statement in the batch layout of
+    bzamd_verify_inner_product_batch_device, and the two legs on them"""
+
+    def __init__(self, worker, n, batch, path):
+        torch, api, dev = worker.torch, worker.api, worker.dev
+        self.torch, self.api, self.n, self.batch = torch, api, n, batch
+        st = {k: np.ascontiguousarray(v).view(np.uint8).reshape(-1) for k, v in np.load(path).items()}
+        self.rounds = max(n - 1, 0).bit_length()
+        pad = np.zeros(32, np.uint8)
+        tile = lambda a: torch.from_numpy(np.tile(a, batch)).to(dev)  # noqa: E731
+        self.b, self.product, self.commit = tile(st["b"]), tile(st["product"]), tile(st["commit"])
+        self.l = tile(st["l"] if self.rounds else pad)
+        self.r = tile(st["r"] if self.rounds else pad)
+        self.ap, self.t0 = tile(st["ap"]), tile(st["t0"])
+        self.tampered_at = batch // 2
+        self.ap_tampered = self.ap.clone()
+        self.ap_tampered[32 * self.tampered_at] ^= 1
+        self.transcripts = torch.zeros_like(self.t0)
+        self.verdicts = torch.zeros(batch, dtype=torch.int32, device=dev)
+        self.has_batch = hasattr(api.load(), "bzamd_verify_inner_product_batch_device")
+        need = (api.inner_product_verify_batch_workspace_bytes(n, batch) if self.has_batch
+                else api.inner_product_verify_workspace_bytes(n))
+        self.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+
+    def single_loop(self, stream, ap):
+        n, rounds, at = self.n, self.rounds, lambda t: t.data_ptr()  # noqa: E731
+        single = self.api.inner_product_verify_workspace_bytes(n)
+        for i in range(self.batch):
+            self.api.verify_inner_product_device(
+                n, 0, at(self.b) + 32 * n * i, at(self.product) + 32 * i, at(self.commit) + 160 * i,
+                at(self.l) + 32 * rounds * i, at(self.r) + 32 * rounds * i, at(ap) + 32 * i,
+                at(self.transcripts) + 203 * i, at(self.verdicts) + 4 * i, at(self.workspace),
+                single, stream=stream.cuda_stream)
+
+    def batch_call(self, stream, ap):
+        at = lambda t: t.data_ptr()  # noqa: E731
+        self.api.verify_inner_product_batch_device(
+            self.n, self.batch, 0, at(self.b), at(self.product), at(self.commit), at(self.l),
+            at(self.r), at(ap), at(self.transcripts), at(self.verdicts), at(self.workspace),
+            self.workspace.numel(), stream=stream.cuda_stream)
+
+    def sample(self, leg, tampered):
+        """-> {"us", "verdicts_ok"}: resetting the transcripts and the verdicts and reading them
+        back are outside the clock"""
+        torch = self.torch
+        self.transcripts.copy_(self.t0)
+        want = torch.ones_like(self.verdicts)
+        if tampered:
+            want[self.tampered_at] = 0
+        self.verdicts.copy_(1 - want)  # the opposite of what is expected
+        torch.cuda.synchronize()
+        ap = self.ap_tampered if tampered else self.ap
+        run = self.single_loop if leg == "single" else self.batch_call
+        us = sample_us(torch, lambda stream: run(stream, ap))
+        return {"us": us, "verdicts_ok": bool((self.verdicts == want).all())}
+
+
+def serve_inner_product():
+    """a child of the inner-product legs: one process, one library (BLITZAR_AMD_LIB)"""
+    from inner_product_bench import Worker
+    worker = Worker()
+    print(json.dumps({"ready": True, "library": worker.api.LIB_PATH}), flush=True)
+    state = None
+    for line in sys.stdin:
+        words = line.split()
+        if not words or words[0] == "quit":
+            break
+        if words[0] == "statement":
+            worker.make_statement(int(words[1]), words[2])
+            print(json.dumps({"ok": True}), flush=True)
+        elif words[0] == "setup":
+            state = None  # (frees the previous batch first)
+            state = InnerProductBatch(worker, int(words[1]), int(words[2]), words[3])
+            print(json.dumps({"ok": True}), flush=True)
+        else:
+            print(json.dumps(state.sample(words[1], tampered=len(words) > 2)), flush=True)
+
+
+def inner_product_legs(args, emit):
+    from inner_product_bench import Child  # (its worker entry is replaced below)
+
+    class IpChild(Child):
+        def __init__(self, library):
+            env = dict(os.environ)
+            if library is not None:
+                env["BLITZAR_AMD_LIB"] = os.path.abspath(library)
+            else:
+                env.pop("BLITZAR_AMD_LIB", None)
+            self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--ip-worker"],
+                                      stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True,
+                                      env=env, cwd=ROOT)
+            self.hello = self.reply()
+
+    assert os.path.exists(args.parent_lib), "--parent-lib: no such library"
+    parent, mine = IpChild(args.parent_lib), IpChild(None)
+    legs = [("ip_single_loop_parent", parent, "single"), ("ip_batch_device", mine, "batch")]
+    tmp = tempfile.TemporaryDirectory()
+    try:
+        for shape in args.inner_product.split("/"):
+            n, batches = shape.split(":")
+            n = int(n)
+            path = os.path.join(tmp.name, f"statement_{n}.npz")
+            mine.ask(f"statement {n} {path}")
+            for batch in (int(x) for x in batches.split(",")):
+                for _, child, _ in legs:
+                    child.ask(f"setup {n} {batch} {path}")
+                for name, child, leg in legs * 2:  # two untimed runs of every leg
+                    assert child.ask(f"sample {leg}")["verdicts_ok"], f"{name}: an intact batch"
+                us = {name: [] for name, _, _ in legs}
+                for _ in range(args.samples):
+                    for name, child, leg in legs:
+                        got = child.ask(f"sample {leg}")
+                        assert got["verdicts_ok"], f"{name} rejected a proof of an intact batch"
+                        us[name].append(got["us"])
+                for name, child, leg in legs:
+                    assert child.ask(f"sample {leg} tampered")["verdicts_ok"], \
+                        f"{name}: not exactly the tampered proof was rejected"
+                    emit({"n": n, "batch": batch, "leg": name, "samples": args.samples,
+                          "median_us": round(statistics.median(us[name]), 1),
+                          "min_us": round(min(us[name]), 1), "max_us": round(max(us[name]), 1)})
+    finally:
+        for child in (parent, mine):
+            child.close()
+        tmp.cleanup()
+
+
 def sample_us(torch, leg):
     stream = torch.cuda.current_stream()
     start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -198,11 +339,15 @@ def main():
     ap.add_argument("--commitments", default="8,1024")
     ap.add_argument("--samples", type=int, default=15)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "verifier_bench.jsonl"))
+    ap.add_argument("--parent-lib")
+    ap.add_argument("--inner-product", default="1024:1,16,256/65536:1,16,64")
+    ap.add_argument("--legs", default="sumcheck,combine,inner_product")
+    ap.add_argument("--ip-worker", action="store_true")
     args = ap.parse_args()
-    from inner_product_bench import Worker  # torch first, then the library, the GPU backend
-    worker = Worker()
-    torch, api = worker.torch, worker.api
-    assert hasattr(api.load(), "bzamd_combine_commitments_device"), "this build has no verifier"
+    if args.ip_worker:
+        serve_inner_product()
+        return
+    wanted = args.legs.split(",")
 
     def emit(rec):
         line = json.dumps(rec)
@@ -210,6 +355,16 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "a") as fh:
             fh.write(line + "\n")
+
+    # (children of their own, before this process opens the device)
+    if "inner_product" in wanted and args.parent_lib:
+        inner_product_legs(args, emit)
+    if "sumcheck" not in wanted and "combine" not in wanted:
+        return
+    from inner_product_bench import Worker  # torch first, then the library, the GPU backend
+    worker = Worker()
+    torch, api = worker.torch, worker.api
+    assert hasattr(api.load(), "bzamd_combine_commitments_device"), "this build has no verifier"
 
     def run(legs, common):
         """legs: [(name, callable)], taken in turn"""
@@ -224,7 +379,7 @@ def main():
                   "median_us": round(statistics.median(us[name]), 1),
                   "min_us": round(min(us[name]), 1), "max_us": round(max(us[name]), 1)})
 
-    for field_id in (0, 1):
+    for field_id in (0, 1) if "sumcheck" in wanted else ():
         for batch in [int(x) for x in args.batches.split(",")]:
             b = Batch(torch, api, field_id, batch, args.variables, args.degree)
             common = {"field_id": field_id, "batch": batch, "variables": args.variables,
@@ -233,7 +388,7 @@ def main():
             b.verify_results()
             run([("check_host", b.check_host), ("check_device", b.check_device)], common)
             b.verify_results()
-    for count in [int(x) for x in args.commitments.split(",")]:
+    for count in [int(x) for x in args.commitments.split(",")] if "combine" in wanted else []:
         c = Combination(torch, api, count)
         run([("combine_device", c.combine_device)], {"commitments": count})
         torch.cuda.synchronize()
