@@ -55,7 +55,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-I" + ROOT,
 #     Z = 1 loop into three waves without a spill (159 VGPRs, 25 s_nop left: 0.578 -> 0.567 ms, a
 #     sequence on resident generators 0.869 -> 0.855 ms per call) but spills 92 bytes in the
 #     caller-generators loop, which then loses in a sequence (0.966 -> 0.975) what it gains alone
-#     (0.623 -> 0.605);
+#     (0.623 -> 0.605); the Z = 1 loop with its rows gathered through LDS keeps the strategy (156
+#     VGPRs, 25 s_nop) as long as the kernel names three waves per SIMD as its upper bound as well
+#     (kernels.h, k_accumulate: otherwise the scheduler aims at four and leaves 413 s_nop);
 #   * the other curve25519 kernels are latency chains on few wavefronts (k_reduce, k_horner): max-ilp
 #     0.198 -> 0.183 and 0.189 -> 0.183 ms, a lone config-2 call 1.187 -> 1.155 ms;
 #   * the other Weierstrass kernels keep the default (grumpkin's k_reduce: +23 % under max-ilp).

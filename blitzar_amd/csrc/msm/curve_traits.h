@@ -234,6 +234,8 @@ struct ed25519_niels_msm : ed25519_msm {
   }
   BZ_HD static point first(const addend& q, bool negate) { return ed29::from_niels(q, negate); }
   static constexpr bool has_signed_gather = false; // 36-byte limb pieces: no aligned exchange
+  // k_accumulate fetches a wavefront's 64 rows as whole lines into LDS (msm/lds_gather.h)
+  static constexpr bool has_lds_gather = true;
   // an accumulated entry against Z = 1 addends relative to the per-call (Y+X, Y-X, Z, 2dT) form
   // (7 of 8 field products, nothing to unpack: plan.h, choose_call_table)
   static constexpr double call_table_entry_cost = 0.88;

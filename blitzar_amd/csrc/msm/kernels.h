@@ -32,6 +32,7 @@
 
 #include "blitzar_amd/csrc/msm/batch_tree.h"
 #include "blitzar_amd/csrc/msm/curve_traits.h"
+#include "blitzar_amd/csrc/msm/lds_gather.h"
 #include "blitzar_amd/csrc/msm/plan.h"
 #include "blitzar_amd/csrc/msm/recode.h"
 #include "blitzar_amd/csrc/msm/tile_digest.h"
@@ -1450,12 +1451,175 @@ template <class P> __device__ __forceinline__ P wave_shfl_down(const P& v, u32 d
 // wave priorities (s_setprio, 0..3) of the two tail kernels, see k_reduce
 constexpr int kReducePrio = 3;
 constexpr int kHornerPrio = 3;
+// The loop for traits with C::has_lds_gather (Z = 1 curve25519 addends): the same walk, but the 64
+// rows a wavefront adds next arrive as whole lines in the wavefront's own LDS region
+// (msm/lds_gather.h) instead of in each lane's registers, so a wave-instruction asks for ~10 lines,
+// 112 bytes of each, and not for 16 bytes of 64 lines, and no part of a row lives in registers
+// across the addition.
+//
+// INVARIANT: the fetch is cooperative, so a wavefront that runs the loop keeps all 64 lanes in it
+// for `trips` rounds, the entry count of lane 0 (segments are consecutive and only the task's last
+// one is short, so no lane of the wavefront has more).  A lane whose entries have run out, or that
+// never had one (lo >= total), keeps handing the row it fetched last to the next round
+// (lds_gather::valid_entry) -- a lane without entries starts from lane 0's first row -- so every row
+// index that reaches an address was read from the task's sorted entries.  Such a lane is masked out
+// of the addition, the flush and the head logic (`act`, `has`).  A wavefront without any entry
+// returns before the first cooperative operation: that test is wave-uniform.
 template <class C>
-__global__ void __launch_bounds__(kAccumulateThreads, C::accumulate_launch_waves)
+__device__ __forceinline__ void
+accumulate_lds_gather(typename C::point* __restrict__ bucket_sums, typename C::point* __restrict__ heads,
+                      const u32* __restrict__ bucket_end, const u32* __restrict__ segment_bucket,
+                      const u32* __restrict__ sorted, const typename C::addend* __restrict__ addends,
+                      const task_desc* __restrict__ tasks) {
+  namespace lg = lds_gather;
+  static_assert(sizeof(typename C::addend) == 128 && sizeof(typename C::operand) >= lg::kRowBytes);
+  static_assert(!C::has_signed_gather);
+  __shared__ __attribute__((aligned(16))) u8 regions[kAccumulateThreads / 64][lg::kRegionBytes];
+  const task_desc task = tasks[blockIdx.y];
+  const u32* ends = bucket_end + task.bucket_base;
+  const u32 total = ends[task.num_buckets - 1];
+  const u32 lane = threadIdx.x & 63;
+  const u32 seg = blockIdx.x * kAccumulateThreads + threadIdx.x;
+  const u32 seg_entries = 1u << task.segment_log2; // 8..128 (plan.h, choose_segment_log2)
+  const u32 lo = seg << task.segment_log2;
+  const u32 wave_lo = __builtin_amdgcn_readfirstlane(lo); // lane 0's
+  if (wave_lo >= total) return;
+  const u32 trips = lg::wave_trips(wave_lo, seg_entries, total);
+  const bool has = lo < total;
+  const u32 hi = lg::lane_hi(lo, seg_entries, total);
+  u32 b = has ? segment_bucket[task.segment_base + seg] : 0;
+  u32 b_end = ends[b];
+  const u32 b_start = b == 0 ? 0 : ends[b - 1];
+  bool owned = has && b_start == lo;
+  const bool whole = has && !owned && b_end >= lo + seg_entries;
+  const u32* idx = sorted + task.entry_base;
+  typename C::point* sums = bucket_sums + task.bucket_base;
+  typename C::point acc = C::identity();
+  const u32 last_bucket = task.num_buckets - 1;
+  u32 next_end = ends[b < last_bucket ? b + 1 : last_bucket];
+  typename C::point* flush_to = owned ? sums + b : heads + task.segment_base + seg;
+
+  u8* region = regions[threadIdx.x >> 6];
+  // one round: the rows of all 64 lanes, kPieces LDS-DMA instructions of 64 pieces each
+  auto issue = [&](u32 entry) {
+    const u32 row = entry & 0x7fffffffu;
+    u32 rows[lg::kPieces]; // (all exchanges first: one wait for the seven, not one each)
+#pragma unroll
+    for (u32 i = 0; i < lg::kPieces; ++i) {
+      rows[i] = static_cast<u32>(
+          __shfl(static_cast<int>(row), static_cast<int>(lg::piece_of(i, lane).source_lane), 64));
+    }
+#pragma unroll
+    for (u32 i = 0; i < lg::kPieces; ++i) {
+      const u8* src = reinterpret_cast<const u8*>(addends) +
+                      static_cast<u64>(rows[i]) * sizeof(typename C::addend) +
+                      lg::piece_of(i, lane).chunk * lg::kPieceBytes;
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)src,
+          (__attribute__((address_space(3))) void*)(region + lg::instruction_base(i)),
+          lg::kPieceBytes, 0, 0);
+    }
+  };
+  // the round in flight has landed -> this lane's row; the region is free again when this returns
+  // (the reads have delivered), and it is the wavefront's own, so no barrier
+  // (the waits are the builtin, which hipcc's own wait bookkeeping reads -- after an s_waitcnt
+  // written in an asm statement it waits again, vmcnt(0), at the first use of a loaded value,
+  // behind the flush block's stores and the load of next_end; gfx9 encoding: vmcnt [3:0] and
+  // [15:14], expcnt [6:4], lgkmcnt [11:8]; the empty asm statements keep the LDS reads between them)
+  constexpr int kWaitVm0 = 0x0f70, kWaitLgkm0 = 0xc07f;
+  auto land = [&]() {
+    __builtin_amdgcn_s_waitcnt(kWaitVm0);
+    asm volatile("" ::: "memory");
+    typename C::operand q;
+    u32* w = reinterpret_cast<u32*>(&q);
+#pragma unroll
+    for (u32 j = 0; j < lg::kPieces; ++j) {
+      const uint4 v = *reinterpret_cast<const uint4*>(region + lg::read_offset(lane, j));
+      w[4 * j] = v.x, w[4 * j + 1] = v.y, w[4 * j + 2] = v.z, w[4 * j + 3] = v.w;
+    }
+    __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
+    asm volatile("" ::: "memory");
+    return C::stage(q);
+  };
+
+  // an entry is sign << 31 | row; e_cur stays a valid entry in every lane (see INVARIANT)
+  u32 e_cur = has ? *(idx + lo) : 0;
+  const u32 wave_entry = static_cast<u32>(__shfl(static_cast<int>(e_cur), 0, 64));
+  e_cur = lg::valid_entry(has, e_cur, wave_entry);
+  issue(e_cur);
+  u32 e_next = lo + 1 < hi ? *(idx + lo + 1) : 0;
+  {
+    const typename C::operand q = land();
+    const bool negate = (e_cur >> 31) != 0;
+    e_cur = lg::valid_entry(lo + 1 < hi, e_next, e_cur);
+    if (trips > 1) issue(e_cur);
+    if (lo + 2 < hi) e_next = *(idx + lo + 2);
+    acc = C::first(q, negate);
+    if constexpr (C::first_pinned) {
+      u32* w = reinterpret_cast<u32*>(&acc);
+#pragma unroll
+      for (u32 k = 0; k < sizeof(acc) / 4; ++k) asm volatile("" : "+v"(w[k]));
+    }
+  }
+  for (u32 k = 1; k < trips; ++k) {
+    const u32 i = lo + k;
+    const bool act = i < hi;
+    // everything the previous iteration asked for is waited for here, in one place: the round, the
+    // entry after next and the end of the next bucket (a use of a loaded value further down would
+    // drain the round in flight with it)
+    const typename C::operand q = land();
+    const bool negate = (e_cur >> 31) != 0;
+    e_cur = lg::valid_entry(i + 1 < hi, e_next, e_cur);
+    if (act && i == b_end) {
+      *flush_to = acc;
+      ++b;
+      b_end = next_end;
+      while (b_end == i) { // empty buckets
+        ++b;
+        b_end = ends[b];
+      }
+      flush_to = sums + b;
+      owned = true;
+      acc = C::identity();
+    }
+    next_end = ends[b < last_bucket ? b + 1 : last_bucket];
+    if (k + 1 < trips) issue(e_cur); // (wave-uniform: nothing is in flight when the kernel ends)
+    if (i + 2 < hi) e_next = *(idx + i + 2);
+    if (act) C::accumulate(acc, q, negate);
+  }
+  // runs of `whole` lanes (necessarily of one bucket) -> one head per run and wavefront
+  const unsigned long long whole_mask = __ballot(whole);
+  bool write_head = has && !owned;
+  if ((whole_mask & (whole_mask >> 1)) != 0) {
+    const u32 run = whole ? static_cast<u32>(__ffsll(static_cast<long long>(~(whole_mask >> lane)))) - 1 : 0;
+    for (u32 d = 1; d < 64; d <<= 1) {
+      const typename C::point other = wave_shfl_down(acc, d);
+      if (whole && d < run) acc = C::add(acc, other);
+    }
+    if (whole && lane != 0 && ((whole_mask >> (lane - 1)) & 1) != 0) write_head = false;
+  }
+  if (owned || write_head) *flush_to = acc;
+}
+
+template <class C> inline constexpr bool kHasLdsGather = requires { requires C::has_lds_gather; };
+
+// (With the rows out of the registers the loop's pressure in source order falls below the 128
+// VGPRs of four waves per SIMD, hipcc's scheduler then takes four waves for its target and throws
+// away every schedule of the addition that needs more, leaving ~400 s_nop in it: the cooperative
+// form names its three waves as the most as well.  This attribute is what the second argument of
+// __launch_bounds__ expands to; 0 = no upper bound.)
+template <class C>
+__global__ void __launch_bounds__(kAccumulateThreads)
+    __attribute__((amdgpu_waves_per_eu(C::accumulate_launch_waves,
+                                       kHasLdsGather<C> ? C::accumulate_launch_waves : 0)))
     k_accumulate(typename C::point* __restrict__ bucket_sums, typename C::point* __restrict__ heads,
                  const u32* __restrict__ bucket_end, const u32* __restrict__ segment_bucket,
                  const u32* __restrict__ sorted, const typename C::addend* __restrict__ addends,
                  const task_desc* __restrict__ tasks) {
+  if constexpr (kHasLdsGather<C>) {
+    accumulate_lds_gather<C>(bucket_sums, heads, bucket_end, segment_bucket, sorted, addends, tasks);
+    return;
+  }
   const task_desc task = tasks[blockIdx.y];
   const u32* ends = bucket_end + task.bucket_base;
   const u32 total = ends[task.num_buckets - 1];

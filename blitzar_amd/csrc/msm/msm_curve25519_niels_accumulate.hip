@@ -1,7 +1,9 @@
 // gfx950 code object of k_accumulate for curve25519 generators in their Z = 1 form (resident sets,
-// built-in generators, fixed-base handles): a translation unit of its own because this loop, unlike
-// the caller-generators one, fits three waves per SIMD under the iterative-ilp scheduling strategy
-// (159 VGPRs, no spill, 1361 -> 1172 instructions per addition; blitzar_amd/build.py, TU_FLAGS).
+// built-in generators, fixed-base handles, caller tables): a translation unit of its own because
+// this loop, unlike the 8-product one, fits three waves per SIMD under the iterative-ilp scheduling
+// strategy.  Its rows arrive by wavefront through LDS (kernels.h, accumulate_lds_gather): 156 VGPRs,
+// no spill, 28 672 bytes of LDS per workgroup, 1215 instructions per addition of which 25 s_nop
+// (blitzar_amd/build.py, TU_FLAGS; tests/test_accumulate_lds_gather_resources.py).
 #include "blitzar_amd/csrc/msm/curve_traits.h"
 #include "blitzar_amd/csrc/msm/kernels.h"
 
