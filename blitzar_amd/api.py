@@ -235,6 +235,25 @@ def load():
         lib.bzamd_evaluate_columns_workspace_bytes.restype = u64
         lib.bzamd_evaluate_columns_device.argtypes = [vp, cu, vp, vp, vp, u64, vp]
         lib.bzamd_evaluate_columns_device.restype = None
+    if hasattr(lib, "bzamd_batch_quotients_device"):
+        lib.bzamd_fold_polynomial.argtypes = [vp, vp, vp, cu, vp, u64, vp, cu]
+        lib.bzamd_fold_polynomial.restype = None
+        lib.bzamd_fold_polynomial_device.argtypes = [vp, vp, vp, cu, vp, u64, vp, cu, vp]
+        lib.bzamd_fold_polynomial_device.restype = None
+        lib.bzamd_evaluate_polynomials.argtypes = [vp, cu, vp, vp, u64, cu, vp, cu]
+        lib.bzamd_evaluate_polynomials.restype = None
+        lib.bzamd_evaluate_polynomials_workspace_bytes.argtypes = [cu, u64, cu, cu]
+        lib.bzamd_evaluate_polynomials_workspace_bytes.restype = u64
+        lib.bzamd_evaluate_polynomials_device.argtypes = [vp, cu, vp, vp, u64, cu, vp, cu, vp, u64,
+                                                          vp]
+        lib.bzamd_evaluate_polynomials_device.restype = None
+        lib.bzamd_batch_quotients.argtypes = [vp, vp, cu, vp, vp, u64, cu, vp, vp, cu]
+        lib.bzamd_batch_quotients.restype = None
+        lib.bzamd_batch_quotients_workspace_bytes.argtypes = [cu, u64, cu, cu]
+        lib.bzamd_batch_quotients_workspace_bytes.restype = u64
+        lib.bzamd_batch_quotients_device.argtypes = [vp, vp, cu, vp, vp, u64, cu, vp, vp, cu, vp,
+                                                     u64, vp]
+        lib.bzamd_batch_quotients_device.restype = None
     if hasattr(lib, "bzamd_combine_commitments_device"):
         lib.bzamd_verify_sumcheck_device.argtypes = [vp, vp, vp, vp, cu, vp, cu, cu, cu, vp]
         lib.bzamd_verify_sumcheck_device.restype = None
@@ -960,6 +979,130 @@ def evaluate_columns_device(field_id, descriptors, vector_ptr, n, evaluations_pt
         None if vector_ptr is None else int(vector_ptr), ctypes.byref(e),
         None if workspace_ptr is None else int(workspace_ptr), workspace_bytes,
         None if stream is None else ctypes.c_void_p(int(stream)))
+
+
+def folded_layout(n, num_variables):
+    """[(offset, length)] in rows of P_1 .. P_{num_variables - 1} inside `folded`: len_0 = n,
+    len_i = ceil(len_{i-1} / 2), off_1 = 0, off_{i+1} = off_i + len_i"""
+    out, offset, length = [], 0, int(n)
+    for _ in range(1, num_variables):
+        length = (length + 1) // 2
+        out.append((offset, length))
+        offset += length
+    return out
+
+
+def _folded_rows(n, num_variables):
+    return sum(length for _, length in folded_layout(n, num_variables))
+
+
+def _device_ptr(p):
+    return None if p is None else int(p)
+
+
+def _stream(stream):
+    return None if stream is None else ctypes.c_void_p(int(stream))
+
+
+def fold_polynomial(field_id, polynomial, point, n=None, num_variables=None, scalars=True,
+                    evaluation=True):
+    """bzamd_fold_polynomial (host operands, either backend).  polynomial: uint8 [n, 32]; point:
+    uint8 [num_variables, 32]; scalars, evaluation: True for a fresh buffer, a uint8 buffer the
+    call may write, or None for a null pointer
+    -> (folded uint8 [rows, 32], scalars uint8 [rows, 32] or None, evaluation uint8 [32] or None)
+    with rows = sum of folded_layout's lengths"""
+    polynomial = np.ascontiguousarray(polynomial, dtype=np.uint8)
+    point = np.ascontiguousarray(point, dtype=np.uint8)
+    n = polynomial.size // 32 if n is None else n
+    num_variables = point.size // 32 if num_variables is None else num_variables
+    rows = _folded_rows(n, num_variables) if 1 <= num_variables <= 30 and n >= 1 else 0
+    folded = np.zeros((max(rows, 1), 32), dtype=np.uint8)
+    if scalars is True:
+        scalars = np.zeros((max(rows, 1), 32), dtype=np.uint8)
+    if evaluation is True:
+        evaluation = np.zeros(32, dtype=np.uint8)
+    load().bzamd_fold_polynomial(_ptr(folded), _ptr(scalars), _ptr(evaluation), field_id,
+                                 _ptr(polynomial), n, _ptr(point), num_variables)
+    return folded[:rows], None if scalars is None else scalars[:rows], evaluation
+
+
+def fold_polynomial_device(field_id, folded_ptr, scalars_ptr, evaluation_ptr, polynomial_ptr, n,
+                           point_ptr, num_variables, stream=None):
+    """bzamd_fold_polynomial_device: enqueue only.  Every *_ptr is memory of the current device as
+    an integer (None: a null pointer); `stream` a hipStream_t as an integer (None: the default
+    stream)."""
+    load().bzamd_fold_polynomial_device(
+        _device_ptr(folded_ptr), _device_ptr(scalars_ptr), _device_ptr(evaluation_ptr), field_id,
+        _device_ptr(polynomial_ptr), n, _device_ptr(point_ptr), num_variables, _stream(stream))
+
+
+def evaluate_polynomials(field_id, polynomial, folded, points, num_variables, n=None):
+    """bzamd_evaluate_polynomials (host operands, either backend).  polynomial: uint8 [n, 32];
+    folded: what fold_polynomial returns; points: uint8 [num_points, 32]
+    -> uint8 [num_points, num_variables, 32]: P_i(u_k) at [k, i]"""
+    polynomial = np.ascontiguousarray(polynomial, dtype=np.uint8)
+    folded = np.ascontiguousarray(folded, dtype=np.uint8)
+    points = np.ascontiguousarray(points, dtype=np.uint8)
+    n = polynomial.size // 32 if n is None else n
+    num_points = points.size // 32
+    evaluations = np.zeros((max(num_points, 1), max(num_variables, 1), 32), dtype=np.uint8)
+    load().bzamd_evaluate_polynomials(_ptr(evaluations), field_id, _ptr(polynomial),
+                                      _ptr(folded) if folded.size else None, n, num_variables,
+                                      _ptr(points), num_points)
+    return evaluations[:num_points, :num_variables]
+
+
+def evaluate_polynomials_workspace_bytes(field_id, n, num_variables, num_points):
+    """bzamd_evaluate_polynomials_workspace_bytes: needs no backend"""
+    return load().bzamd_evaluate_polynomials_workspace_bytes(field_id, n, num_variables, num_points)
+
+
+def evaluate_polynomials_device(field_id, evaluations_ptr, polynomial_ptr, folded_ptr, n,
+                                num_variables, points_ptr, num_points, workspace_ptr,
+                                workspace_bytes, stream=None):
+    """bzamd_evaluate_polynomials_device: enqueue only; pointers and stream as
+    fold_polynomial_device"""
+    load().bzamd_evaluate_polynomials_device(
+        _device_ptr(evaluations_ptr), field_id, _device_ptr(polynomial_ptr),
+        _device_ptr(folded_ptr), n, num_variables, _device_ptr(points_ptr), num_points,
+        _device_ptr(workspace_ptr), workspace_bytes, _stream(stream))
+
+
+def batch_quotients(field_id, polynomial, folded, q, points, num_variables, n=None,
+                    remainders=True):
+    """bzamd_batch_quotients (host operands, either backend).  q: uint8 [32]; remainders: True for
+    a fresh buffer, a uint8 buffer the call may write, or None for a null pointer
+    -> (quotients uint8 [num_points, n, 32] in scalar form, remainders uint8 [num_points, 32] or
+    None)"""
+    polynomial = np.ascontiguousarray(polynomial, dtype=np.uint8)
+    folded = np.ascontiguousarray(folded, dtype=np.uint8)
+    points = np.ascontiguousarray(points, dtype=np.uint8)
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    n = polynomial.size // 32 if n is None else n
+    num_points = points.size // 32
+    quotients = np.zeros((max(num_points, 1), max(int(n), 1), 32), dtype=np.uint8)
+    if remainders is True:
+        remainders = np.zeros((max(num_points, 1), 32), dtype=np.uint8)
+    load().bzamd_batch_quotients(_ptr(quotients), _ptr(remainders), field_id, _ptr(polynomial),
+                                 _ptr(folded) if folded.size else None, n, num_variables, _ptr(q),
+                                 _ptr(points), num_points)
+    return quotients[:num_points, :n], remainders
+
+
+def batch_quotients_workspace_bytes(field_id, n, num_variables, num_points):
+    """bzamd_batch_quotients_workspace_bytes: needs no backend"""
+    return load().bzamd_batch_quotients_workspace_bytes(field_id, n, num_variables, num_points)
+
+
+def batch_quotients_device(field_id, quotients_ptr, remainders_ptr, polynomial_ptr, folded_ptr, n,
+                           num_variables, q_ptr, points_ptr, num_points, workspace_ptr,
+                           workspace_bytes, stream=None):
+    """bzamd_batch_quotients_device: enqueue only; pointers and stream as fold_polynomial_device"""
+    load().bzamd_batch_quotients_device(
+        _device_ptr(quotients_ptr), _device_ptr(remainders_ptr), field_id,
+        _device_ptr(polynomial_ptr), _device_ptr(folded_ptr), n, num_variables,
+        _device_ptr(q_ptr), _device_ptr(points_ptr), num_points, _device_ptr(workspace_ptr),
+        workspace_bytes, _stream(stream))
 
 
 class MultiexpHandle:

@@ -25,6 +25,7 @@
 #include "blitzar_amd/csrc/fixed/handle.h"
 #include "blitzar_amd/csrc/proof/inner_product.h"
 #include "blitzar_amd/csrc/proof/mle_opening.h"
+#include "blitzar_amd/csrc/proof/univariate_opening.h"
 #include "blitzar_amd/csrc/proof/sumcheck.h"
 #include "blitzar_amd/csrc/proof/sumcheck_transcript.h"
 #include "blitzar_amd/csrc/proof/transcript.h"
@@ -2138,6 +2139,99 @@ void bzamd_evaluate_columns_device(void* evaluations, unsigned field_id, const v
   proof::evaluate_columns_device(evaluations, field_id, vector,
                                  proof::column_evaluation{cols.data(), e->num_columns, e->n},
                                  workspace, workspace_bytes, on);
+}
+
+// the field work of a HyperKZG opening between its MSM calls (proof/univariate_opening.hip).  The
+// device forms with a workspace check their arguments before they ask for the backend
+void bzamd_fold_polynomial(void* folded, void* scalars, void* evaluation, unsigned field_id,
+                           const void* polynomial, uint64_t n, const void* point,
+                           unsigned num_variables) {
+  check_arguments("bzamd_fold_polynomial", polynomial != nullptr && point != nullptr &&
+                                               (folded != nullptr || num_variables <= 1));
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::fold_polynomial(st, scalars, evaluation, field_id,
+                         proof::univariate_opening{polynomial, folded, n, num_variables, point, 0});
+}
+
+void bzamd_fold_polynomial_device(void* folded, void* scalars, void* evaluation, unsigned field_id,
+                                  const void* polynomial, uint64_t n, const void* point,
+                                  unsigned num_variables, void* stream) {
+  check_arguments("bzamd_fold_polynomial_device", polynomial != nullptr && point != nullptr &&
+                                                      (folded != nullptr || num_variables <= 1));
+  proof::fold_polynomial_device(
+      scalars, evaluation, field_id,
+      proof::univariate_opening{polynomial, folded, n, num_variables, point, 0},
+      device_form(stream).stream);
+}
+
+void bzamd_evaluate_polynomials(void* evaluations, unsigned field_id, const void* polynomial,
+                                const void* folded, uint64_t n, unsigned num_variables,
+                                const void* points, unsigned num_points) {
+  check_arguments("bzamd_evaluate_polynomials",
+                  evaluations != nullptr && polynomial != nullptr && points != nullptr &&
+                      (folded != nullptr || num_variables <= 1));
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::evaluate_polynomials(st, evaluations, field_id,
+                              proof::univariate_opening{polynomial, const_cast<void*>(folded), n,
+                                                        num_variables, points, num_points});
+}
+
+uint64_t bzamd_evaluate_polynomials_workspace_bytes(unsigned field_id, uint64_t n,
+                                                    unsigned num_variables, unsigned num_points) {
+  return proof::evaluate_polynomials_workspace_bytes(field_id, n, num_variables, num_points);
+}
+
+void bzamd_evaluate_polynomials_device(void* evaluations, unsigned field_id, const void* polynomial,
+                                       const void* folded, uint64_t n, unsigned num_variables,
+                                       const void* points, unsigned num_points, void* workspace,
+                                       uint64_t workspace_bytes, void* stream) {
+  check_arguments("bzamd_evaluate_polynomials_device",
+                  evaluations != nullptr && polynomial != nullptr && points != nullptr &&
+                      workspace != nullptr && (folded != nullptr || num_variables <= 1));
+  const proof::univariate_opening o{polynomial, const_cast<void*>(folded), n, num_variables, points,
+                                    num_points};
+  proof::check_evaluate_polynomials_device(evaluations, field_id, o, workspace, workspace_bytes);
+  proof::evaluate_polynomials_device(evaluations, field_id, o, workspace, workspace_bytes,
+                                     device_form(stream).stream);
+}
+
+void bzamd_batch_quotients(void* quotients, void* remainders, unsigned field_id,
+                           const void* polynomial, const void* folded, uint64_t n,
+                           unsigned num_variables, const void* q, const void* points,
+                           unsigned num_points) {
+  check_arguments("bzamd_batch_quotients",
+                  quotients != nullptr && polynomial != nullptr && q != nullptr &&
+                      points != nullptr && (folded != nullptr || num_variables <= 1));
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::batch_quotients(st, quotients, remainders, field_id,
+                         proof::univariate_opening{polynomial, const_cast<void*>(folded), n,
+                                                   num_variables, points, num_points},
+                         q);
+}
+
+uint64_t bzamd_batch_quotients_workspace_bytes(unsigned field_id, uint64_t n,
+                                               unsigned num_variables, unsigned num_points) {
+  return proof::batch_quotients_workspace_bytes(field_id, n, num_variables, num_points);
+}
+
+void bzamd_batch_quotients_device(void* quotients, void* remainders, unsigned field_id,
+                                  const void* polynomial, const void* folded, uint64_t n,
+                                  unsigned num_variables, const void* q, const void* points,
+                                  unsigned num_points, void* workspace, uint64_t workspace_bytes,
+                                  void* stream) {
+  check_arguments("bzamd_batch_quotients_device",
+                  quotients != nullptr && polynomial != nullptr && q != nullptr &&
+                      points != nullptr && workspace != nullptr &&
+                      (folded != nullptr || num_variables <= 1));
+  const proof::univariate_opening o{polynomial, const_cast<void*>(folded), n, num_variables, points,
+                                    num_points};
+  proof::check_batch_quotients_device(quotients, remainders, field_id, o, q, workspace,
+                                      workspace_bytes);
+  proof::batch_quotients_device(quotients, remainders, field_id, o, q, workspace, workspace_bytes,
+                                device_form(stream).stream);
 }
 
 //--------------------------------------------------------------------------------------------------

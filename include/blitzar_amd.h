@@ -687,6 +687,91 @@ void bzamd_evaluate_columns_device(void* evaluations, unsigned field_id, const v
                                    const struct bzamd_column_evaluation* e, void* workspace,
                                    uint64_t workspace_bytes, void* stream);
 
+/* Univariate openings: the field work of a HyperKZG prover between its MSM calls, for a polynomial
+ * of l = num_variables variables given by its n evaluations (the combined column of
+ * bzamd_combine_columns, say).  Exact field arithmetic in both fields (field_id 0 or 1; anything
+ * else aborts).  The transcript and the commitment key stay with the caller.
+ *
+ * Element form: 32 bytes in the representation sxt_prove_sumcheck takes for the field (field 0 the
+ * little-endian integer mod l, field 1 four little-endian 64-bit words of x 2^256 mod p); inputs
+ * may be unreduced, outputs are canonical.  Scalar form: the canonical value as a plain 32-byte
+ * little-endian integer, what an MSM descriptor with element_nbytes 32 reads (field 0: the same
+ * bytes as element form).
+ *
+ * Sizes: 1 <= l <= 30 and 1 <= n <= 2^l.  P_0 = polynomial has n rows and rows past the end are
+ * zero.  len_0 = n, len_i = ceil(len_{i-1} / 2); off_1 = 0, off_{i+1} = off_i + len_i.  `folded`
+ * holds P_1 .. P_{l-1} back to back, P_i at row off_i with len_i rows: off_l <= n + l rows in all,
+ * none for l = 1 (folded may then be NULL).
+ *
+ * Fold.  With x_0 .. x_{l-1} = point, for i = 1 .. l - 1 and j < len_i
+ *   P_i[j] = P_{i-1}[2j] + x_{l-i} (P_{i-1}[2j+1] - P_{i-1}[2j]),
+ * P_{i-1}[2j+1] being 0 when 2j + 1 = len_{i-1}.  `folded` is written in element form; `scalars`
+ * (may be NULL) takes the same rows in scalar form, the input of the commitments to P_1 .. P_{l-1};
+ * `evaluation` (may be NULL; 32 bytes, element form) takes the same step once more, with x_0 on
+ * P_{l-1}: x_0 binds the top bit of the row index and x_{l-1} the lowest, so that evaluation =
+ * sum_i P_0[i] vector[i] with the vector of bzamd_mle_evaluation_vector for the same point, exactly
+ * (l = 1, n = 1: (1 - x_0) P_0[0]).
+ *
+ * Evaluate.  Points u_0 .. u_{t-1}, 1 <= t = num_points <= 4 (HyperKZG: r, -r, r^2):
+ *   evaluations[k l + i] = sum_{j < len_i} P_i[j] u_k^j,   element form, u^0 = 1 for u = 0 too.
+ *
+ * Batch and divide.  One element q and the same points:
+ *   B[m]   = sum_{i < l, m < len_i} q^i P_i[m],        m < n,
+ *   h_k[j] = sum_{m = j+1}^{n-1} B[m] u_k^(m-j-1),     j < n   (h_k[n-1] = 0 is written),
+ * `quotients`: t x n rows in scalar form, h_k at row k n; `remainders` (may be NULL): t elements,
+ * element form, B(u_k).  B(X) = (X - u_k) h_k(X) + remainders[k], and remainders[k] =
+ * sum_i q^i evaluations[k l + i].
+ *
+ * polynomial, folded, scalars and quotients must be 8-byte aligned; point, points, q, evaluation,
+ * evaluations, remainders and workspace need no alignment.  Aborts, before anything is launched: a
+ * null pointer other than those named as optional, l outside [1, 30], n outside [1, 2^l],
+ * num_points outside [1, 4], a misaligned array, a workspace that is too small, and an output that
+ * overlaps an input of the same call. */
+/* HOST operands, blocking, cpu and gpu backends.  The gpu backend uploads the operands, runs the
+ * device form on memory of the call's own, synchronises once and downloads the results. */
+void bzamd_fold_polynomial(void* folded, void* scalars, void* evaluation, unsigned field_id,
+                           const void* polynomial, uint64_t n, const void* point,
+                           unsigned num_variables);
+/* DEVICE pointers on the current HIP device, all of them.  gpu backend only.  The call only
+ * enqueues on `stream`: no synchronise, no allocation, no callback, no workspace.  The operands
+ * are read in stream order, so the call may follow the producer of `polynomial` and `point` on the
+ * same stream with no synchronise in between.  ceil(l / 10) kernel launches, whatever n is. */
+void bzamd_fold_polynomial_device(void* folded, void* scalars, void* evaluation, unsigned field_id,
+                                  const void* polynomial, uint64_t n, const void* point,
+                                  unsigned num_variables, void* stream);
+
+void bzamd_evaluate_polynomials(void* evaluations, unsigned field_id, const void* polynomial,
+                                const void* folded, uint64_t n, unsigned num_variables,
+                                const void* points, unsigned num_points);
+/* What the device form needs as workspace: one partial sum per point and chunk of rows, at most
+ * 2080 x 36 x num_points + 512 bytes whatever n is.  Needs no backend; 0 for an unsupported field
+ * and for sizes outside the limits above. */
+uint64_t bzamd_evaluate_polynomials_workspace_bytes(unsigned field_id, uint64_t n,
+                                                    unsigned num_variables, unsigned num_points);
+/* DEVICE pointers, as bzamd_fold_polynomial_device, which it may follow on the same stream with no
+ * synchronise in between; workspace: at least bzamd_evaluate_polynomials_workspace_bytes of the
+ * same arguments, and a later call on the same stream may use the same one.  Two kernel launches. */
+void bzamd_evaluate_polynomials_device(void* evaluations, unsigned field_id, const void* polynomial,
+                                       const void* folded, uint64_t n, unsigned num_variables,
+                                       const void* points, unsigned num_points, void* workspace,
+                                       uint64_t workspace_bytes, void* stream);
+
+void bzamd_batch_quotients(void* quotients, void* remainders, unsigned field_id,
+                           const void* polynomial, const void* folded, uint64_t n,
+                           unsigned num_variables, const void* q, const void* points,
+                           unsigned num_points);
+/* What the device form needs as workspace: B is made on the fly and never stored, so it is a sum
+ * and a carry per point and chunk of rows, at most 2 x 1024 x 36 x num_points + 768 bytes whatever
+ * n is.  Needs no backend; 0 for an unsupported field and for sizes outside the limits above. */
+uint64_t bzamd_batch_quotients_workspace_bytes(unsigned field_id, uint64_t n,
+                                               unsigned num_variables, unsigned num_points);
+/* DEVICE pointers, as bzamd_evaluate_polynomials_device.  Three kernel launches, whatever n is. */
+void bzamd_batch_quotients_device(void* quotients, void* remainders, unsigned field_id,
+                                  const void* polynomial, const void* folded, uint64_t n,
+                                  unsigned num_variables, const void* q, const void* points,
+                                  unsigned num_points, void* workspace, uint64_t workspace_bytes,
+                                  void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
