@@ -228,6 +228,11 @@ def load():
         lib.bzamd_combine_columns.restype = None
         lib.bzamd_combine_columns_device.argtypes = [vp, vp, cu, vp, vp]
         lib.bzamd_combine_columns_device.restype = None
+    if hasattr(lib, "bzamd_invert_columns_device"):
+        lib.bzamd_invert_columns.argtypes = [vp, vp, cu, vp]
+        lib.bzamd_invert_columns.restype = None
+        lib.bzamd_invert_columns_device.argtypes = [vp, vp, cu, vp, vp]
+        lib.bzamd_invert_columns_device.restype = None
     if hasattr(lib, "bzamd_evaluate_columns_device"):
         lib.bzamd_evaluate_columns.argtypes = [vp, cu, vp, vp]
         lib.bzamd_evaluate_columns.restype = None
@@ -939,6 +944,49 @@ def combine_columns_device(field_id, descriptors, coefficients_ptr, n, combined_
     load().bzamd_combine_columns_device(
         int(combined_ptr), None if product_ptr is None else int(product_ptr), field_id,
         ctypes.byref(c), None if stream is None else ctypes.c_void_p(int(stream)))
+
+
+class bzamd_column_inversion(ctypes.Structure):
+    _fields_ = [("columns", ctypes.POINTER(sxt_sequence_descriptor)),
+                ("coefficients", ctypes.c_void_p), ("shift", ctypes.c_void_p),
+                ("num_columns", ctypes.c_uint), ("n", ctypes.c_uint64)]
+
+
+def invert_columns(field_id, columns, n, coefficients=None, shift=None, want_scalars=False):
+    """bzamd_invert_columns (host operands, either backend).  columns: as combine_columns;
+    coefficients: uint8 [num_columns, 32] (None: every coefficient is 1); shift: uint8 [32] (None:
+    0) -> inverses uint8 [n, 32] in element form, 1 / (shift + sum_j coefficients[j] column_j[i])
+    with 0 for a zero denominator; want_scalars: (inverses, scalars), the same rows in scalar
+    form"""
+    descs, keep = make_descriptors(_column_pairs(columns))
+    if coefficients is not None:
+        coefficients = np.ascontiguousarray(coefficients, dtype=np.uint8)
+    if shift is not None:
+        shift = np.ascontiguousarray(shift, dtype=np.uint8)
+    inverses = np.zeros((max(int(n), 1), 32), dtype=np.uint8)
+    scalars = np.zeros((max(int(n), 1), 32), dtype=np.uint8) if want_scalars else None
+    v = bzamd_column_inversion(descs, None if coefficients is None else coefficients.ctypes.data,
+                               None if shift is None else shift.ctypes.data, len(keep), n)
+    load().bzamd_invert_columns(_ptr(inverses), _ptr(scalars), field_id, ctypes.byref(v))
+    return (inverses[:n], scalars[:n]) if want_scalars else inverses[:n]
+
+
+def invert_columns_device(field_id, inverses_ptr, scalars_ptr, descriptors, coefficients_ptr,
+                          shift_ptr, n, stream=None):
+    """bzamd_invert_columns_device: enqueue only, one kernel launch.  descriptors: one (device_ptr,
+    n_j, nbytes, signed) per column, or a ready sxt_sequence_descriptor array (the one the MSM
+    took); every *_ptr is memory of the current device as an integer (None: a null pointer);
+    `stream` a hipStream_t as an integer (None: the default stream)."""
+    if isinstance(descriptors, ctypes.Array):
+        descs, num_columns = descriptors, len(descriptors)
+    else:
+        descs, num_columns = _device_descriptors(descriptors)
+    v = bzamd_column_inversion(descs, None if coefficients_ptr is None else int(coefficients_ptr),
+                               None if shift_ptr is None else int(shift_ptr), num_columns, n)
+    load().bzamd_invert_columns_device(
+        None if inverses_ptr is None else int(inverses_ptr),
+        None if scalars_ptr is None else int(scalars_ptr), field_id, ctypes.byref(v),
+        None if stream is None else ctypes.c_void_p(int(stream)))
 
 
 class bzamd_column_evaluation(ctypes.Structure):

@@ -36,6 +36,7 @@ SOURCES = [
     "proof/sumcheck_columns.hip",
     "proof/sumcheck_transcript.hip",
     "proof/mle_opening.hip",
+    "proof/column_inverse.hip",
     "proof/univariate_opening.hip",
     "proof/verify_opening.hip",
     "api/capi.hip",

@@ -24,6 +24,7 @@
 #include "blitzar_amd/csrc/fixed/dump.h"
 #include "blitzar_amd/csrc/fixed/handle.h"
 #include "blitzar_amd/csrc/proof/inner_product.h"
+#include "blitzar_amd/csrc/proof/column_inverse.h"
 #include "blitzar_amd/csrc/proof/mle_opening.h"
 #include "blitzar_amd/csrc/proof/univariate_opening.h"
 #include "blitzar_amd/csrc/proof/sumcheck.h"
@@ -2103,6 +2104,45 @@ void bzamd_combine_columns_device(void* combined, void* product, unsigned field_
       combination_form_columns("bzamd_combine_columns_device", combined, c);
   proof::combine_columns_device(combined, product, field_id, combination_of(*c, cols),
                                 device_form(stream).stream);
+}
+
+namespace {
+// the inversion's columns, checked as in prove_sumcheck_columns_entry
+extern "C++" std::vector<proof::sumcheck_column> inversion_form_columns(
+    const char* name, const void* inverses, const void* scalars,
+    const struct bzamd_column_inversion* v) {
+  check_arguments(name, v != nullptr && (inverses != nullptr || scalars != nullptr));
+  BZ_RELEASE_ASSERT(v->num_columns >= 1 && v->num_columns <= proof::kMaxInvertedColumns,
+                    "the column inversion needs 1 <= num_columns <= 32");
+  return checked_sumcheck_columns(v->columns, v->num_columns);
+}
+proof::column_inversion inversion_of(const struct bzamd_column_inversion& v,
+                                     const std::vector<proof::sumcheck_column>& cols) {
+  return {cols.data(), v.coefficients, v.shift, v.num_columns, v.n};
+}
+} // namespace
+
+// the inverse column of a log-derivative argument (proof/column_inverse.hip).  The device form
+// checks its arguments before it asks for the backend
+void bzamd_invert_columns(void* inverses, void* scalars, unsigned field_id,
+                          const struct bzamd_column_inversion* v) {
+  const std::vector<proof::sumcheck_column> cols =
+      inversion_form_columns("bzamd_invert_columns", inverses, scalars, v);
+  const proof::column_inversion inversion = inversion_of(*v, cols);
+  proof::check_column_inversion(inverses, scalars, field_id, inversion);
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::invert_columns(st, inverses, scalars, field_id, inversion);
+}
+
+void bzamd_invert_columns_device(void* inverses, void* scalars, unsigned field_id,
+                                 const struct bzamd_column_inversion* v, void* stream) {
+  const std::vector<proof::sumcheck_column> cols =
+      inversion_form_columns("bzamd_invert_columns_device", inverses, scalars, v);
+  const proof::column_inversion inversion = inversion_of(*v, cols);
+  proof::check_column_inversion(inverses, scalars, field_id, inversion);
+  proof::invert_columns_device(inverses, scalars, field_id, inversion,
+                               device_form(stream).stream);
 }
 
 namespace {

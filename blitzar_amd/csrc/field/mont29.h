@@ -445,7 +445,10 @@ template <class P> struct mont29 {
   // With A = a R the loop yields A^-1 2^k mod p (log2 p <= k <= 2 log2 p) as a plain integer; two
   // products by powers of two take the 2^k out (x 2^m / R each, m1 + m2 = 2 LB N - k), one with R^3
   // makes it a^-1 R.
-  BZ_HD_NOINLINE static fe invert(const fe& a) {
+  BZ_HD_NOINLINE static fe invert(const fe& a) { return invert_inline(a); }
+  // The same, expanded in place: for a kernel that holds many values in registers across its one
+  // inversion (proof/column_inverse.hip), which a call would send through scratch memory.
+  BZ_HD static fe invert_inline(const fe& a) {
     const fe ac = canonical(norm(a));
     u32 any = 0;
     for (int i = 0; i < N; ++i) any |= ac.v[i];

@@ -648,6 +648,46 @@ void bzamd_combine_columns(void* combined, void* product, unsigned field_id,
 void bzamd_combine_columns_device(void* combined, void* product, unsigned field_id,
                                   const struct bzamd_column_combination* c, void* stream);
 
+/* The column of inverses a log-derivative argument (lookup, membership, join, group-by) commits to
+ * and multiplies in its sumcheck:
+ *   denominator[i] = shift + sum_j coefficients[j] * column_j[i]        i < n
+ *   inverses[i]    = denominator[i]^-1, and 0 where denominator[i] = 0
+ * A zero denominator disturbs no other row.  The columns mean what they mean in
+ * bzamd_combine_columns and are validated by the same rule: columns[j].n <= n rows (longer aborts),
+ * rows past a column's end are zero (their denominator is `shift` plus the other columns), n = 0
+ * with data = NULL is a zero column; element_nbytes 1 .. 31 little-endian integers, two's
+ * complement when is_signed (up to 16 bytes); element_nbytes 32 the field's elements, unreduced
+ * values included; data at any address.  `coefficients` (NULL: every coefficient is 1) and `shift`
+ * (NULL: 0) are in element form, need no alignment and may be unreduced.  `inverses` (n x 32 bytes)
+ * is written in element form, canonical; `scalars` (n x 32 bytes) takes the same rows in scalar
+ * form, what bzamd_msm_device reads as a 32-byte column (the two forms are defined above
+ * bzamd_fold_polynomial: field 0 the same bytes, field 1 Montgomery words and plain integers).
+ * Either output may be NULL, not both; both must be 8-byte aligned.
+ * 1 <= n <= 2^30, 1 <= num_columns <= 32: the descriptors of a call travel as kernel arguments; a
+ * caller with more columns combines them with bzamd_combine_columns_device first and inverts that
+ * one 32-byte column.  field_id 0 or 1.  Aborts, before anything is launched: a null v, columns or
+ * both outputs null, a bad descriptor, a column longer than n, a limit exceeded, a misaligned
+ * output, an output that overlaps an input or the other output, an unsupported field id. */
+struct bzamd_column_inversion {
+  const struct sxt_sequence_descriptor* columns; /* num_columns descriptors */
+  const void* coefficients; /* may be NULL: every coefficient is 1; else num_columns x 32 bytes */
+  const void* shift;        /* may be NULL: 0; else 32 bytes */
+  unsigned num_columns;
+  uint64_t n;
+};
+/* HOST operands (columns[j].data included), blocking, cpu and gpu backends.  The cpu backend shares
+ * one inversion among 256 rows; the gpu backend uploads the columns at their own width, runs the
+ * device form, synchronises once and downloads the outputs. */
+void bzamd_invert_columns(void* inverses, void* scalars, unsigned field_id,
+                          const struct bzamd_column_inversion* v);
+/* DEVICE pointers on the current HIP device: inverses, scalars, coefficients, shift and every
+ * columns[j].data (read in stream order, never written).  HOST: the struct and the descriptors,
+ * which are read before the call returns.  gpu backend only (anything else aborts).  The call only
+ * enqueues on `stream`: no synchronise, no allocation, no callback, no workspace.  ONE kernel
+ * launch, whatever n, num_columns and the data are. */
+void bzamd_invert_columns_device(void* inverses, void* scalars, unsigned field_id,
+                                 const struct bzamd_column_inversion* v, void* stream);
+
 /* The MLE evaluations of typed columns, given the evaluation vector of the point:
  *   evaluations[j] = sum_{i < columns[j].n} column_j[i] * vector[i],
  * num_columns x 32 bytes, written canonical (no alignment needed).  With the vector of
