@@ -22,9 +22,11 @@ struct ed29_cached {
 };
 
 // resident addend of a generator set that is registered once and reused (built-in generators,
-// bzamd_generators, sxt_multiexp_handle): normalised to Z = 1, (y+x, y-x, 2dxy), padded to one
-// 128-byte line.  One field product and 80 bytes of gather traffic less per addition than
-// ed29_cached; the normalisation costs an inversion per generator, once.
+// bzamd_generators, sxt_multiexp_handle) and of the caller tables: normalised to Z = 1 and stored
+// HALVED, ((y+x)/2, (y-x)/2, d x y), all B ~ 1, padded to one 128-byte line.  (`T2d` keeps its name:
+// it holds half of 2dxy.)  One field product and 80 bytes of gather traffic less per addition than
+// ed29_cached; halved, the addition needs neither the doubling of Z nor a weak reduction
+// (add_niels).  The normalisation costs an inversion per generator, once.
 struct alignas(16) ed29_niels {
   fe29 YpX, YmX, T2d;
   u32 pad[5];
@@ -182,49 +184,58 @@ BZ_HD ed29_point add(const ed29_point& p, const ed29_point& q) {
   return add_cached(p, to_cached(q), false);
 }
 
-BZ_HD ed29_niels to_niels(const ed29_point& p) {
-  const fe29 zinv = f29::invert(p.Z);
-  const fe29 x = f29::mul(p.X, zinv);
-  const fe29 y = f29::mul(p.Y, zinv);
+// (X : Y : Z) with 1 / Z -> the halved Z = 1 addend ((y+x)/2, (y-x)/2, d x y); X and Y may be any
+// operand of a product with a B ~ 1 value.  The halving rides on the normalisation factor: one
+// product by 1 / 2 = (p + 1) / 2, and d x y = (2 * x/2) * (y/2) * 2d.
+BZ_HD ed29_niels niels_of_scaled(const fe29& big_x, const fe29& big_y, const fe29& zinv) {
+  const fe29 zh = f29::mul(zinv, f29::const_inv2());           // 1 / (2 Z)
+  const fe29 xh = f29::mul(big_x, zh);                         // x / 2
+  const fe29 yh = f29::mul(big_y, zh);                         // y / 2
   ed29_niels n;
-  n.YpX = f29::weak_reduce(f29::add(y, x));
-  n.YmX = f29::weak_reduce(f29::sub(y, x));
-  n.T2d = f29::mul(f29::mul(x, y), f29::const_2d());
+  n.YpX = f29::weak_reduce(f29::add(yh, xh));                  // B 2 -> 1
+  n.YmX = f29::weak_reduce(f29::sub(yh, xh));                  // B 3 -> 1
+  n.T2d = f29::mul(f29::mul(f29::add(xh, xh), yh), f29::const_2d()); // 2 * 1, 1 * 1
   for (int i = 0; i < 5; ++i) n.pad[i] = 0;
   return n;
 }
 
-// p + q (q negated when `negate`) for a Z = 1 addend: 7 field products
+BZ_HD ed29_niels to_niels(const ed29_point& p) {
+  return niels_of_scaled(p.X, p.Y, f29::invert(p.Z));
+}
+
+// p + q (q negated when `negate`) for a halved Z = 1 addend: 7 field products.  With the addend
+// halved, A, B, C and D = Z of the unified addition all come out halved, so E, F, G, H do and the
+// result is (X3/4 : Y3/4 : Z3/4 : T3/4): the same point, without doubling Z.  C enters negated
+// (the conditional negation takes the opposite sign), so that F = D - C is a sum (B 2) and
+// G = D + C the difference (B 3): every product sits at B(f) B(g) <= 6 with no weak reduction.
 BZ_HD ed29_point add_niels(const ed29_point& p, const ed29_niels& q, bool negate) {
-  const fe29 qa = f29::select(q.YpX, q.YmX, negate);
-  const fe29 qb = f29::select(q.YmX, q.YpX, negate);
-  const fe29 qt = f29::cneg_xad(q.T2d, negate);                // B 2
+  const fe29 qa = f29::select(q.YpX, q.YmX, negate);           // B 1
+  const fe29 qb = f29::select(q.YmX, q.YpX, negate);           // B 1
+  const fe29 qt = f29::cneg_xad(q.T2d, !negate);               // -(d x y) of +-q, B 2
   const fe29 a = f29::mul(f29::add(p.Y, p.X), qa);             // 2 * 1
   const fe29 b = f29::mul(f29::sub(p.Y, p.X), qb);             // 3 * 1
-  const fe29 c = f29::mul(p.T, qt);                            // 1 * 2
-  const fe29 d = f29::add(p.Z, p.Z);                           // B 2
-  const fe29 ez = f29::add(d, c);                              // B 3
-  const fe29 et = f29::weak_reduce(f29::sub(d, c));            // B 4 -> 1
+  const fe29 cn = f29::mul(p.T, qt);                           // 1 * 2   (-C)
+  const fe29 et = f29::add(p.Z, cn);                           // B 2     Z - C
+  const fe29 ez = f29::sub(p.Z, cn);                           // B 3     Z + C
   const fe29 ex = f29::sub(a, b);                              // B 3
   const fe29 ey = f29::add(a, b);                              // B 2
   ed29_point r;
-  r.X = f29::mul(ex, et);
-  r.Y = f29::mul(ey, ez);
-  r.Z = f29::mul(ez, et);
-  r.T = f29::mul(ex, ey);
+  r.X = f29::mul(ex, et); // 3 * 2
+  r.Y = f29::mul(ey, ez); // 2 * 3
+  r.Z = f29::mul(ez, et); // 3 * 2
+  r.T = f29::mul(ex, ey); // 3 * 2
   return r;
 }
 
-// identity + q (q negated when `negate`) for a Z = 1 addend: (2x : 2y : 2 : 2xy)
+// identity + q (q negated when `negate`) for a halved Z = 1 addend: (x : y : 1 : x y), all B ~ 1
 BZ_HD ed29_point from_niels(const ed29_niels& q, bool negate) {
   const fe29 qa = f29::select(q.YpX, q.YmX, negate);
   const fe29 qb = f29::select(q.YmX, q.YpX, negate);
   ed29_point r;
-  r.X = f29::weak_reduce(f29::sub(qa, qb));
-  r.Y = f29::weak_reduce(f29::add(qa, qb));
-  r.Z = f29::zero();
-  r.Z.v[0] = 2;
-  r.T = f29::mul(f29::cneg_xad(q.T2d, negate), f29::const_dinv());
+  r.X = f29::weak_reduce(f29::sub(qa, qb));                           // B 3 -> 1
+  r.Y = f29::weak_reduce(f29::add(qa, qb));                           // B 2 -> 1
+  r.Z = f29::one();
+  r.T = f29::mul(f29::cneg_xad(q.T2d, negate), f29::const_dinv());    // 2 * 1
   return r;
 }
 

@@ -346,5 +346,9 @@ BZ_HD fe29 const_2d() { return from_fe51(f51::const_2d()); }
 BZ_HD fe29 const_dinv() { return from_fe51(f51::const_dinv()); }
 BZ_HD fe29 const_sqrtm1() { return from_fe51(f51::const_sqrtm1()); }
 BZ_HD fe29 const_invsqrtamd() { return from_fe51(f51::const_invsqrtamd()); }
+// 1 / 2 = (p + 1) / 2 = 2^254 - 9
+BZ_HD fe29 const_inv2() {
+  return {{kMask - 8, kMask, kMask, kMask, kMask, kMask, kMask, kMask, (1u << 22) - 1}};
+}
 } // namespace f29
 } // namespace bz

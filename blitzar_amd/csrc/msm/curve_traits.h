@@ -224,8 +224,8 @@ struct ed25519_msm {
 
 // curve25519 against generators that are normalised once and then kept: a *resident* set (built-in
 // generators, bzamd_generators, handles) or the context's caller table of a keyed caller pointer
-// (engine.h, caller_slot: a tile is normalised again only when its bytes change).  Z = 1 addends of
-// 128 bytes, 7 instead of 8 products per addition
+// (engine.h, caller_slot: a tile is normalised again only when its bytes change).  Halved Z = 1
+// addends of 128 bytes (curve/ed29.h, ed29_niels), 7 instead of 8 products per addition
 struct ed25519_niels_msm : ed25519_msm {
   using addend = ed29_niels;
   static constexpr int accumulate_launch_waves = accumulate_waves_per_simd;
@@ -279,15 +279,10 @@ struct ed25519_niels_msm : ed25519_msm {
   BZ_HD static addend addend_from_point(const point& p, const fe29& zinv, bool) {
     return niels_of(p.X, p.Y, zinv);
   }
+  // the halved form ((y+x)/2, (y-x)/2, d x y) that add_niels / from_niels take: one sequence of
+  // operations with ed29::to_niels
   BZ_HD static addend niels_of(const fe29& big_x, const fe29& big_y, const fe29& zinv) {
-    const fe29 x = f29::mul(big_x, zinv);
-    const fe29 y = f29::mul(big_y, zinv);
-    ed29_niels n;
-    n.YpX = f29::weak_reduce(f29::add(y, x));
-    n.YmX = f29::weak_reduce(f29::sub(y, x));
-    n.T2d = f29::mul(f29::mul(x, y), f29::const_2d());
-    for (int k = 0; k < 5; ++k) n.pad[k] = 0;
-    return n;
+    return ed29::niels_of_scaled(big_x, big_y, zinv);
   }
 };
 

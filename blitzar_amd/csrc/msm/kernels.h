@@ -1465,17 +1465,23 @@ constexpr int kHornerPrio = 3;
 // index that reaches an address was read from the task's sorted entries.  Such a lane is masked out
 // of the addition, the flush and the head logic (`act`, `has`).  A wavefront without any entry
 // returns before the first cooperative operation: that test is wave-uniform.
-template <class C>
+//
+// Piece addresses: while every row of the task lies in the table's first 4 GiB
+// (lds_gather::narrow_offsets: resident sets, caller tables, the headline) a piece is the
+// wave-uniform table base plus a 32-bit lane offset row << 7 | chunk << 4, the saddr + voffset form
+// of global_load_lds: one 32-bit instruction per piece.  A merged window table may reach 2^31 rows;
+// `Wide` keeps the 64-bit address per piece for those launches.  k_accumulate holds both loops and
+// picks by task, wave-uniformly.
+template <class C, bool Wide>
 __device__ __forceinline__ void
 accumulate_lds_gather(typename C::point* __restrict__ bucket_sums, typename C::point* __restrict__ heads,
                       const u32* __restrict__ bucket_end, const u32* __restrict__ segment_bucket,
                       const u32* __restrict__ sorted, const typename C::addend* __restrict__ addends,
-                      const task_desc* __restrict__ tasks) {
+                      const task_desc& task, u8* region) {
   namespace lg = lds_gather;
-  static_assert(sizeof(typename C::addend) == 128 && sizeof(typename C::operand) >= lg::kRowBytes);
+  static_assert(sizeof(typename C::addend) == lg::kStoredRowBytes &&
+                sizeof(typename C::operand) >= lg::kRowBytes);
   static_assert(!C::has_signed_gather);
-  __shared__ __attribute__((aligned(16))) u8 regions[kAccumulateThreads / 64][lg::kRegionBytes];
-  const task_desc task = tasks[blockIdx.y];
   const u32* ends = bucket_end + task.bucket_base;
   const u32 total = ends[task.num_buckets - 1];
   const u32 lane = threadIdx.x & 63;
@@ -1499,7 +1505,6 @@ accumulate_lds_gather(typename C::point* __restrict__ bucket_sums, typename C::p
   u32 next_end = ends[b < last_bucket ? b + 1 : last_bucket];
   typename C::point* flush_to = owned ? sums + b : heads + task.segment_base + seg;
 
-  u8* region = regions[threadIdx.x >> 6];
   // one round: the rows of all 64 lanes, kPieces LDS-DMA instructions of 64 pieces each
   auto issue = [&](u32 entry) {
     const u32 row = entry & 0x7fffffffu;
@@ -1511,9 +1516,13 @@ accumulate_lds_gather(typename C::point* __restrict__ bucket_sums, typename C::p
     }
 #pragma unroll
     for (u32 i = 0; i < lg::kPieces; ++i) {
-      const u8* src = reinterpret_cast<const u8*>(addends) +
-                      static_cast<u64>(rows[i]) * sizeof(typename C::addend) +
-                      lg::piece_of(i, lane).chunk * lg::kPieceBytes;
+      const u8* src = reinterpret_cast<const u8*>(addends);
+      if constexpr (Wide) {
+        src += static_cast<u64>(rows[i]) * sizeof(typename C::addend) +
+               lg::piece_of(i, lane).chunk * lg::kPieceBytes;
+      } else {
+        src += static_cast<u64>(lg::piece_offset32(rows[i], lg::piece_of(i, lane).chunk));
+      }
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)src,
           (__attribute__((address_space(3))) void*)(region + lg::instruction_base(i)),
@@ -1617,7 +1626,19 @@ __global__ void __launch_bounds__(kAccumulateThreads)
                  const u32* __restrict__ sorted, const typename C::addend* __restrict__ addends,
                  const task_desc* __restrict__ tasks) {
   if constexpr (kHasLdsGather<C>) {
-    accumulate_lds_gather<C>(bucket_sums, heads, bucket_end, segment_bucket, sorted, addends, tasks);
+    namespace lg = lds_gather;
+    __shared__ __attribute__((aligned(16))) u8 regions[kAccumulateThreads / 64][lg::kRegionBytes];
+    // (the wavefront's index as a scalar: the seven landing bases of a round are then scalar sums,
+    // not a vector add and a v_readfirstlane each)
+    u8* region = regions[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
+    const task_desc task = tasks[blockIdx.y];
+    if (__builtin_expect(lg::narrow_offsets(task.row_base, task.rows), 1)) {
+      accumulate_lds_gather<C, false>(bucket_sums, heads, bucket_end, segment_bucket, sorted, addends,
+                                      task, region);
+    } else {
+      accumulate_lds_gather<C, true>(bucket_sums, heads, bucket_end, segment_bucket, sorted, addends,
+                                     task, region);
+    }
     return;
   }
   const task_desc task = tasks[blockIdx.y];

@@ -57,4 +57,20 @@ BZ_HD constexpr u32 wave_trips(u32 wave_lo, u32 seg_entries, u32 total) {
 BZ_HD constexpr u32 valid_entry(bool has_next, u32 next_entry, u32 current_entry) {
   return has_next ? next_entry : current_entry;
 }
+
+// Piece addresses.  A stored row is kStoredRowBytes apart from the next; while every row a task can
+// name (its entries are row_base + row, row < rows: plan.h, task_desc) lies in the table's first
+// 4 GiB, the byte offset of a piece fits 32 bits and is a shift and an OR (chunk < 8), so the fetch
+// takes the wave-uniform table base and this lane offset.  Other tasks (merged window tables, up to
+// 2^31 rows) form the 64-bit address.
+constexpr u32 kStoredRowBytes = 128;
+constexpr u32 kStoredRowLog2 = 7;
+static_assert(kPieces * kPieceBytes <= kStoredRowBytes && (1u << kStoredRowLog2) == kStoredRowBytes);
+BZ_HD constexpr bool narrow_offsets(u64 row_base, u64 rows) {
+  return row_base + rows <= (u64{1} << (32 - kStoredRowLog2));
+}
+// for row < 2^25: the same value as u64(row) * kStoredRowBytes + chunk * kPieceBytes
+BZ_HD constexpr u32 piece_offset32(u32 row, u32 chunk) {
+  return row << kStoredRowLog2 | chunk * kPieceBytes;
+}
 } // namespace bz::lds_gather

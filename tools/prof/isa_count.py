@@ -109,11 +109,18 @@ def analyse(asm_path):
                 labels[lm.group(1)] = k
         # backward branches = loops; the per-entry loop is the first one in code order that holds
         # multiplies (the fold of whole-bucket runs behind it is a loop around one complete addition)
+        # A kernel that holds the loop twice (the Z = 1 loop: 32-bit and 64-bit piece offsets, picked
+        # per task) may branch from the second copy back to a block in front of the first, an exit
+        # both share; that is no loop: only labels hipcc marks as the header of an outermost loop
+        # count.  The first copy in code order is the one counted (the 32-bit form, which the kernel
+        # marks as the expected branch).
         best = None
         for k, line in enumerate(body):
             bm = re.match(r"^\s+s_c?branch\S*\s+(\.LBB\d+_\d+)", line)
             if bm and bm.group(1) in labels and labels[bm.group(1)] < k:
                 lo = labels[bm.group(1)]
+                if not re.search(r"=>\s*This (Inner )?Loop Header: Depth=1\b", body[lo]):
+                    continue
                 if not any("v_mad_u64_u32" in x for x in body[lo:k]):
                     continue
                 if best is None or lo < best[0] or (lo == best[0] and k > best[1]):
