@@ -233,6 +233,15 @@ def load():
         lib.bzamd_invert_columns.restype = None
         lib.bzamd_invert_columns_device.argtypes = [vp, vp, cu, vp, vp]
         lib.bzamd_invert_columns_device.restype = None
+    if hasattr(lib, "bzamd_count_multiplicities_device"):
+        lib.bzamd_count_multiplicities_workspace_bytes.argtypes = [u64]
+        lib.bzamd_count_multiplicities_workspace_bytes.restype = u64
+        lib.bzamd_count_multiplicities.argtypes = [vp, vp, cu, vp]
+        lib.bzamd_count_multiplicities.restype = None
+        lib.bzamd_count_multiplicities_device.argtypes = [vp, vp, cu, vp, vp, u64, vp]
+        lib.bzamd_count_multiplicities_device.restype = None
+        lib.bzamd_multiplicity_first_slot.argtypes = [cu, vp, u64]
+        lib.bzamd_multiplicity_first_slot.restype = u64
     if hasattr(lib, "bzamd_evaluate_columns_device"):
         lib.bzamd_evaluate_columns.argtypes = [vp, cu, vp, vp]
         lib.bzamd_evaluate_columns.restype = None
@@ -986,6 +995,63 @@ def invert_columns_device(field_id, inverses_ptr, scalars_ptr, descriptors, coef
     load().bzamd_invert_columns_device(
         None if inverses_ptr is None else int(inverses_ptr),
         None if scalars_ptr is None else int(scalars_ptr), field_id, ctypes.byref(v),
+        None if stream is None else ctypes.c_void_p(int(stream)))
+
+
+class bzamd_multiplicity_count(ctypes.Structure):
+    _fields_ = [("table", sxt_sequence_descriptor), ("lookups", sxt_sequence_descriptor)]
+
+
+def count_multiplicities_workspace_bytes(table_rows):
+    """bzamd_count_multiplicities_workspace_bytes: no backend needed; 0 outside the limits"""
+    return load().bzamd_count_multiplicities_workspace_bytes(table_rows)
+
+
+def multiplicity_first_slot(field_id, element, table_rows):
+    """bzamd_multiplicity_first_slot: the slot at which the probe for a key starts (a diagnostic;
+    the hash is not part of the ABI).  element: uint8 [32], element form, may be unreduced"""
+    element = np.ascontiguousarray(element, dtype=np.uint8)
+    return load().bzamd_multiplicity_first_slot(field_id, _ptr(element), table_rows)
+
+
+def count_multiplicities(field_id, table, lookups, want_misses=True):
+    """bzamd_count_multiplicities (host operands, either backend).  table, lookups: one column each
+    as in combine_columns (an array or an (array, is_signed) pair); table may be (None, m): the
+    range table 0 .. m - 1 -> (multiplicities uint64 [m], misses), or the multiplicities alone
+    with want_misses False (a null pointer)"""
+    if isinstance(table, tuple) and table[0] is None:
+        table_desc, keep_table = sxt_sequence_descriptor(8, int(table[1]), None, 0), None
+    else:
+        descs, keep_table = make_descriptors(_column_pairs([table]))
+        table_desc = descs[0]
+    descs, keep_lookups = make_descriptors(_column_pairs([lookups]))
+    multiplicities = np.zeros(max(int(table_desc.n), 1), dtype=np.uint64)
+    misses = ctypes.c_uint64(0)
+    c = bzamd_multiplicity_count(table_desc, descs[0])
+    load().bzamd_count_multiplicities(_ptr(multiplicities),
+                                      ctypes.byref(misses) if want_misses else None, field_id,
+                                      ctypes.byref(c))
+    del keep_table, keep_lookups
+    multiplicities = multiplicities[:table_desc.n]
+    return (multiplicities, int(misses.value)) if want_misses else multiplicities
+
+
+def count_multiplicities_device(field_id, multiplicities_ptr, misses_ptr, table, lookups,
+                                workspace_ptr, workspace_bytes, stream=None):
+    """bzamd_count_multiplicities_device: enqueue only, three kernel launches (the range table:
+    two).  table, lookups: one (device_ptr, rows, nbytes, signed) each; a table with device_ptr
+    None is the range table 0 .. rows - 1; every *_ptr is memory of the current device as an
+    integer (None: a null pointer); `stream` a hipStream_t as an integer (None: the default
+    stream)."""
+    def descriptor(column):
+        ptr, rows, nbytes, signed = column
+        return sxt_sequence_descriptor(nbytes, rows, None if ptr is None else int(ptr),
+                                       1 if signed else 0)
+    c = bzamd_multiplicity_count(descriptor(table), descriptor(lookups))
+    load().bzamd_count_multiplicities_device(
+        None if multiplicities_ptr is None else int(multiplicities_ptr),
+        None if misses_ptr is None else int(misses_ptr), field_id, ctypes.byref(c),
+        None if workspace_ptr is None else int(workspace_ptr), workspace_bytes,
         None if stream is None else ctypes.c_void_p(int(stream)))
 
 

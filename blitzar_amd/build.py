@@ -37,6 +37,7 @@ SOURCES = [
     "proof/sumcheck_transcript.hip",
     "proof/mle_opening.hip",
     "proof/column_inverse.hip",
+    "proof/multiplicities.hip",
     "proof/univariate_opening.hip",
     "proof/verify_opening.hip",
     "api/capi.hip",

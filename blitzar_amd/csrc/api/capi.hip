@@ -26,6 +26,7 @@
 #include "blitzar_amd/csrc/proof/inner_product.h"
 #include "blitzar_amd/csrc/proof/column_inverse.h"
 #include "blitzar_amd/csrc/proof/mle_opening.h"
+#include "blitzar_amd/csrc/proof/multiplicities.h"
 #include "blitzar_amd/csrc/proof/univariate_opening.h"
 #include "blitzar_amd/csrc/proof/sumcheck.h"
 #include "blitzar_amd/csrc/proof/sumcheck_transcript.h"
@@ -2143,6 +2144,57 @@ void bzamd_invert_columns_device(void* inverses, void* scalars, unsigned field_i
   proof::check_column_inversion(inverses, scalars, field_id, inversion);
   proof::invert_columns_device(inverses, scalars, field_id, inversion,
                                device_form(stream).stream);
+}
+
+namespace {
+// the count's columns: the lookups checked as in prove_sumcheck_columns_entry, the table too unless
+// its data is null, which names the range table and fixes its width
+proof::multiplicity_count multiplicity_form_columns(const char* name, const void* multiplicities,
+                                                    const struct bzamd_multiplicity_count* c) {
+  check_arguments(name, multiplicities != nullptr && c != nullptr);
+  proof::multiplicity_count count;
+  if (c->table.data == nullptr) {
+    BZ_RELEASE_ASSERT(c->table.element_nbytes == 8 && !c->table.is_signed,
+                      "a NULL table is the range table: element_nbytes 8, unsigned");
+    count.table = proof::sumcheck_column{nullptr, c->table.n, 8, false};
+  } else {
+    count.table = checked_sumcheck_columns(&c->table, 1)[0];
+  }
+  count.lookups = checked_sumcheck_columns(&c->lookups, 1)[0];
+  return count;
+}
+} // namespace
+
+// the multiplicity column of a log-derivative argument (proof/multiplicities.hip).  Both forms check
+// their arguments before they ask for the backend
+uint64_t bzamd_count_multiplicities_workspace_bytes(uint64_t table_rows) {
+  return proof::multiplicity_workspace_bytes(table_rows);
+}
+
+void bzamd_count_multiplicities(void* multiplicities, uint64_t* misses, unsigned field_id,
+                                const struct bzamd_multiplicity_count* c) {
+  const proof::multiplicity_count count =
+      multiplicity_form_columns("bzamd_count_multiplicities", multiplicities, c);
+  proof::check_multiplicity_count(multiplicities, misses, field_id, count, nullptr, 0, false);
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::count_multiplicities(st, static_cast<u64*>(multiplicities), misses, field_id, count);
+}
+
+void bzamd_count_multiplicities_device(void* multiplicities, void* misses, unsigned field_id,
+                                       const struct bzamd_multiplicity_count* c, void* workspace,
+                                       uint64_t workspace_bytes, void* stream) {
+  const proof::multiplicity_count count =
+      multiplicity_form_columns("bzamd_count_multiplicities_device", multiplicities, c);
+  proof::check_multiplicity_count(multiplicities, misses, field_id, count, workspace,
+                                  workspace_bytes, true);
+  proof::count_multiplicities_device(static_cast<u64*>(multiplicities), static_cast<u64*>(misses),
+                                     field_id, count, workspace, device_form(stream).stream);
+}
+
+uint64_t bzamd_multiplicity_first_slot(unsigned field_id, const void* element,
+                                       uint64_t table_rows) {
+  return proof::multiplicity_first_slot(field_id, element, table_rows);
 }
 
 namespace {

@@ -688,6 +688,67 @@ void bzamd_invert_columns(void* inverses, void* scalars, unsigned field_id,
 void bzamd_invert_columns_device(void* inverses, void* scalars, unsigned field_id,
                                  const struct bzamd_column_inversion* v, void* stream);
 
+/* The multiplicity column of a log-derivative argument: how often each row of a table column is
+ * looked up by the rows of a lookup column, so that
+ *   sum_t multiplicities[t] / (alpha + T[t]) = sum_i 1 / (alpha + L[i])      whenever misses = 0.
+ * The key of a row is its value in the field as the canonical integer in [0, p).  Both columns are
+ * the MSM's / sumcheck's descriptors and mean what they mean in bzamd_combine_columns, validated by
+ * the same rule: element_nbytes 1 .. 31 little-endian integers, two's complement when is_signed (up
+ * to 16 bytes); element_nbytes 32 the field's elements, unreduced values included; data at any
+ * address.  Two rows are equal when their keys are: an i8 -1, an i64 -1 and the 32-byte element
+ * p - 1 are one key, x and x + p in a 32-byte column are one key, and in field 1 a 32-byte row
+ * (Montgomery words) and a narrow row compare by value, not by bytes.  The table (m = table.n rows)
+ * and the lookups (n = lookups.n rows) may differ in width and signedness.  Tuples are the caller's
+ * to fold: bzamd_combine_columns_device with the powers of beta makes the one 32-byte column that
+ * bzamd_invert_columns_device inverts, and the same column goes here.
+ *   multiplicities: m x 8 bytes, little-endian uint64_t, 8-byte aligned.  With first(t) the least
+ *     t' whose key equals that of row t:
+ *       multiplicities[t] = #{i < n : key(lookups[i]) = key(table[t])}   when first(t) = t,
+ *       multiplicities[t] = 0                                            otherwise
+ *     (duplicates in the table give their count to the first occurrence, so the identity holds for
+ *     any table).  What bzamd_msm_device, the sumcheck provers and bzamd_combine_columns_device
+ *     read as an 8-byte unsigned column.
+ *   misses (may be NULL; one uint64_t, 8-byte aligned): the number of lookup rows whose key is in
+ *     no table row.  The identity holds exactly when it is 0.
+ * No input is written.
+ * The range table: table.data == NULL with table.n = m >= 1, table.element_nbytes = 8 and
+ * table.is_signed = 0 means T[t] = t (any other width or signedness with a NULL table aborts).  A
+ * lookup row hits row `key` when key < m and misses otherwise; negative narrow values are p - |x|
+ * and miss.  This form needs no workspace (`workspace` may be NULL).
+ * Limits: 1 <= m <= 2^28, 0 <= n <= 2^30 (lookups.n = 0 with data = NULL writes m zeros and
+ * misses = 0); field_id 0 or 1.  Aborts, before anything is launched: a null multiplicities or c,
+ * a bad descriptor, a limit exceeded, a misaligned output, an output that overlaps an input, the
+ * other output or the workspace, a workspace that is too small, an unsupported field id, the
+ * device form on the cpu backend. */
+struct bzamd_multiplicity_count {
+  struct sxt_sequence_descriptor table;   /* m = table.n rows */
+  struct sxt_sequence_descriptor lookups; /* n = lookups.n rows */
+};
+/* What the device form's workspace takes for a table with data: S slots of 4 bytes, S the least
+ * power of two >= 2 table_rows (1 row: 2 slots, 2 rows: 4, 3 rows: 8; there is no minimum), and
+ * 256 bytes for the pointer's alignment.  Needs no backend; 0 outside 1 <= table_rows <= 2^28. */
+uint64_t bzamd_count_multiplicities_workspace_bytes(uint64_t table_rows);
+/* HOST operands (table.data and lookups.data included), blocking, cpu and gpu backends.  The cpu
+ * backend counts row by row; the gpu backend uploads both columns at their own width, runs the
+ * device form on memory of the call's own, synchronises once and downloads the outputs. */
+void bzamd_count_multiplicities(void* multiplicities, uint64_t* misses, unsigned field_id,
+                                const struct bzamd_multiplicity_count* c);
+/* DEVICE pointers on the current HIP device: multiplicities, misses, workspace, table.data and
+ * lookups.data (read in stream order, never written).  HOST: the struct, which is read before the
+ * call returns.  gpu backend only (anything else aborts).  The call only enqueues on `stream`: no
+ * synchronise, no allocation, no callback.  THREE kernel launches (the range table: TWO), whatever
+ * m, n and the data are.  workspace: at least bzamd_count_multiplicities_workspace_bytes(m) bytes
+ * at any address, contents ignored; a later call on the same stream may use the same workspace. */
+void bzamd_count_multiplicities_device(void* multiplicities, void* misses, unsigned field_id,
+                                       const struct bzamd_multiplicity_count* c, void* workspace,
+                                       uint64_t workspace_bytes, void* stream);
+/* A diagnostic, like bzamd_accumulate_form: the slot, below S, at which the probe for a key starts
+ * in the device form's table of table_rows rows, so that tests can build clusters and wrap-arounds
+ * without restating the hash.  element: 32 bytes in element form, may be unreduced.  Host
+ * arithmetic, needs no backend; UINT64_MAX outside the limits (table_rows, field_id) or for a NULL
+ * element.  The hash is NOT part of the ABI and may change between versions. */
+uint64_t bzamd_multiplicity_first_slot(unsigned field_id, const void* element, uint64_t table_rows);
+
 /* The MLE evaluations of typed columns, given the evaluation vector of the point:
  *   evaluations[j] = sum_{i < columns[j].n} column_j[i] * vector[i],
  * num_columns x 32 bytes, written canonical (no alignment needed).  With the vector of
