@@ -59,6 +59,7 @@
 #include <vector>
 
 #include "blitzar_amd/csrc/msm/batch_tree.h"
+#include "blitzar_amd/csrc/proof/host_call.h"
 #include "blitzar_amd/csrc/proof/sumcheck_columns.h"
 
 namespace bz::proof {
@@ -233,19 +234,6 @@ __global__ void __launch_bounds__(kInverseThreads, 2)
 }
 
 //--------------------------------------------------------------------------------------------------
-// checks
-//--------------------------------------------------------------------------------------------------
-struct byte_range {
-  const void* at;
-  u64 bytes;
-};
-bool overlap(const byte_range& a, const byte_range& b) {
-  if (a.at == nullptr || b.at == nullptr || a.bytes == 0 || b.bytes == 0) return false;
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.at), b0 = reinterpret_cast<uintptr_t>(b.at);
-  return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
-//--------------------------------------------------------------------------------------------------
 // host backend: the same arithmetic, Montgomery's trick over blocks of kHostBlock rows
 //--------------------------------------------------------------------------------------------------
 template <class E> void invert_host(u64* inverses, u64* scalars, const column_inversion& v) {
@@ -344,48 +332,20 @@ void invert_columns(api_state& st, void* inverses, void* scalars, unsigned field
       return;
     }
     // the columns up at their own width, the device form, the results down
-    hipStream_t stream = st.primary().stream;
-    BZ_HIP_CHECK(hipSetDevice(st.primary().device));
-    const size_t coefficient_bytes = static_cast<size_t>(32) * v.num_columns;
+    host_call call{st};
     const size_t out_bytes = static_cast<size_t>(32) * v.n;
-    size_t bytes = 2 * device_arena::padded(out_bytes) + device_arena::padded(coefficient_bytes) + 256;
-    for (u32 j = 0; j < v.num_columns; ++j) {
-      bytes += device_arena::padded(v.columns[j].n * v.columns[j].nbytes);
-    }
-    device_arena own;
-    own.reset(bytes, stream);
-    u64* d_inverses = inverses != nullptr ? own.take<u64>(4 * v.n) : nullptr;
-    u64* d_scalars = scalars != nullptr ? own.take<u64>(4 * v.n) : nullptr;
-    u8* d_coefficients = nullptr;
-    u8* d_shift = nullptr;
-    if (v.coefficients != nullptr) {
-      d_coefficients = own.take<u8>(coefficient_bytes);
-      BZ_HIP_CHECK(hipMemcpyAsync(d_coefficients, v.coefficients, coefficient_bytes,
-                                  hipMemcpyHostToDevice, stream));
-    }
-    if (v.shift != nullptr) {
-      d_shift = own.take<u8>(32);
-      BZ_HIP_CHECK(hipMemcpyAsync(d_shift, v.shift, 32, hipMemcpyHostToDevice, stream));
-    }
-    std::vector<sumcheck_column> on_device(v.columns, v.columns + v.num_columns);
-    for (sumcheck_column& column : on_device) {
-      const size_t column_bytes = column.n * column.nbytes;
-      u8* staged = own.take<u8>(column_bytes);
-      if (column_bytes != 0) {
-        BZ_HIP_CHECK(hipMemcpyAsync(staged, column.data, column_bytes, hipMemcpyHostToDevice, stream));
-      }
-      column.data = staged;
-    }
+    u64 *d_inverses, *d_scalars;
+    u8 *d_coefficients, *d_shift;
+    std::vector<sumcheck_column> on_device;
+    call.output(&d_inverses, inverses, out_bytes);
+    call.output(&d_scalars, scalars, out_bytes);
+    call.input(&d_coefficients, v.coefficients, static_cast<size_t>(32) * v.num_columns);
+    call.input(&d_shift, v.shift, 32);
+    call.columns(&on_device, v.columns, v.num_columns);
+    call.allocate();
     const column_inversion staged{on_device.data(), d_coefficients, d_shift, v.num_columns, v.n};
-    invert_enqueue<E>(d_inverses, d_scalars, staged, stream);
-    if (inverses != nullptr) {
-      BZ_HIP_CHECK(hipMemcpyAsync(inverses, d_inverses, out_bytes, hipMemcpyDeviceToHost, stream));
-    }
-    if (scalars != nullptr) {
-      BZ_HIP_CHECK(hipMemcpyAsync(scalars, d_scalars, out_bytes, hipMemcpyDeviceToHost, stream));
-    }
-    BZ_HIP_CHECK(hipStreamSynchronize(stream));
-    own.release();
+    invert_enqueue<E>(d_inverses, d_scalars, staged, call.stream());
+    call.finish();
   });
 }
 } // namespace bz::proof

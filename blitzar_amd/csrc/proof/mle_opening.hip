@@ -48,6 +48,7 @@
 #include <utility>
 #include <vector>
 
+#include "blitzar_amd/csrc/proof/host_call.h"
 #include "blitzar_amd/csrc/proof/sumcheck_columns.h"
 
 namespace bz::proof {
@@ -510,19 +511,14 @@ void mle_evaluation_vector(api_state& st, void* vector, unsigned field_id,
       return;
     }
     // the point up, the device form, the vector down: memory of the call's own
-    hipStream_t stream = st.primary().stream;
-    BZ_HIP_CHECK(hipSetDevice(st.primary().device));
-    const size_t point_bytes = static_cast<size_t>(32) * num_variables;
-    const size_t vector_bytes = static_cast<size_t>(32) * n;
-    device_arena own;
-    own.reset(device_arena::padded(point_bytes) + device_arena::padded(vector_bytes), stream);
-    u8* d_point = own.take<u8>(point_bytes);
-    u64* d_vector = own.take<u64>(4 * n);
-    BZ_HIP_CHECK(hipMemcpyAsync(d_point, evaluation_point, point_bytes, hipMemcpyHostToDevice, stream));
-    evaluation_vector_enqueue<E>(d_vector, d_point, num_variables, n, stream);
-    BZ_HIP_CHECK(hipMemcpyAsync(vector, d_vector, vector_bytes, hipMemcpyDeviceToHost, stream));
-    BZ_HIP_CHECK(hipStreamSynchronize(stream));
-    own.release();
+    host_call call{st};
+    u8* d_point;
+    u64* d_vector;
+    call.input(&d_point, evaluation_point, static_cast<size_t>(32) * num_variables);
+    call.output(&d_vector, vector, static_cast<size_t>(32) * n);
+    call.allocate();
+    evaluation_vector_enqueue<E>(d_vector, d_point, num_variables, n, call.stream());
+    call.finish();
   });
 }
 
@@ -545,45 +541,23 @@ void combine_columns(api_state& st, void* combined, void* product, unsigned fiel
       return;
     }
     // the columns up at their own width, the device form, the results down
-    hipStream_t stream = st.primary().stream;
-    BZ_HIP_CHECK(hipSetDevice(st.primary().device));
+    host_call call{st};
+    // the product and the evaluations it is made of: both or neither
     const bool with_product = product != nullptr && c.evaluations != nullptr;
     const size_t element_bytes = static_cast<size_t>(32) * c.num_columns;
-    const size_t combined_bytes = static_cast<size_t>(32) * c.n;
-    size_t bytes = device_arena::padded(combined_bytes) + 2 * device_arena::padded(element_bytes) + 256;
-    for (u32 j = 0; j < c.num_columns; ++j) {
-      bytes += device_arena::padded(c.columns[j].n * c.columns[j].nbytes);
-    }
-    device_arena own;
-    own.reset(bytes, stream);
-    u64* d_combined = own.take<u64>(4 * c.n);
-    u8* d_coefficients = own.take<u8>(element_bytes);
-    u8* d_evaluations = own.take<u8>(element_bytes);
-    u8* d_product = own.take<u8>(32);
-    BZ_HIP_CHECK(hipMemcpyAsync(d_coefficients, c.coefficients, element_bytes, hipMemcpyHostToDevice,
-                                stream));
-    if (with_product) {
-      BZ_HIP_CHECK(hipMemcpyAsync(d_evaluations, c.evaluations, element_bytes, hipMemcpyHostToDevice,
-                                  stream));
-    }
-    std::vector<sumcheck_column> on_device(c.columns, c.columns + c.num_columns);
-    for (sumcheck_column& column : on_device) {
-      const size_t column_bytes = column.n * column.nbytes;
-      u8* staged = own.take<u8>(column_bytes);
-      if (column_bytes != 0) {
-        BZ_HIP_CHECK(hipMemcpyAsync(staged, column.data, column_bytes, hipMemcpyHostToDevice, stream));
-      }
-      column.data = staged;
-    }
-    const column_combination staged{on_device.data(), d_coefficients,
-                                    with_product ? d_evaluations : nullptr, c.num_columns, c.n};
-    combine_enqueue<E>(d_combined, with_product ? d_product : nullptr, staged, stream);
-    BZ_HIP_CHECK(hipMemcpyAsync(combined, d_combined, combined_bytes, hipMemcpyDeviceToHost, stream));
-    if (with_product) {
-      BZ_HIP_CHECK(hipMemcpyAsync(product, d_product, 32, hipMemcpyDeviceToHost, stream));
-    }
-    BZ_HIP_CHECK(hipStreamSynchronize(stream));
-    own.release();
+    u64* d_combined;
+    u8 *d_coefficients, *d_evaluations, *d_product;
+    std::vector<sumcheck_column> on_device;
+    call.output(&d_combined, combined, static_cast<size_t>(32) * c.n);
+    call.input(&d_coefficients, c.coefficients, element_bytes);
+    call.input(&d_evaluations, with_product ? c.evaluations : nullptr, element_bytes);
+    call.output(&d_product, with_product ? product : nullptr, 32);
+    call.columns(&on_device, c.columns, c.num_columns);
+    call.allocate();
+    const column_combination staged{on_device.data(), d_coefficients, d_evaluations, c.num_columns,
+                                    c.n};
+    combine_enqueue<E>(d_combined, d_product, staged, call.stream());
+    call.finish();
   });
 }
 
@@ -615,37 +589,20 @@ void evaluate_columns(api_state& st, void* evaluations, unsigned field_id, const
       return;
     }
     // the vector and the columns up at their own width, the device form, the evaluations down
-    hipStream_t stream = st.primary().stream;
-    BZ_HIP_CHECK(hipSetDevice(st.primary().device));
-    const size_t vector_bytes = static_cast<size_t>(32) * e.n;
-    const size_t evaluation_bytes = static_cast<size_t>(32) * e.num_columns;
+    host_call call{st};
     const size_t workspace_bytes = evaluate_layout<typename E::F>{e.num_columns, e.n}.total;
-    size_t bytes = device_arena::padded(vector_bytes) + device_arena::padded(evaluation_bytes) +
-                   device_arena::padded(workspace_bytes);
-    for (u32 j = 0; j < e.num_columns; ++j) {
-      bytes += device_arena::padded(e.columns[j].n * e.columns[j].nbytes);
-    }
-    device_arena own;
-    own.reset(bytes, stream);
-    u64* d_vector = own.take<u64>(4 * e.n);
-    u8* d_evaluations = own.take<u8>(evaluation_bytes);
-    u8* d_workspace = own.take<u8>(workspace_bytes);
-    BZ_HIP_CHECK(hipMemcpyAsync(d_vector, vector, vector_bytes, hipMemcpyHostToDevice, stream));
-    std::vector<sumcheck_column> on_device(e.columns, e.columns + e.num_columns);
-    for (sumcheck_column& column : on_device) {
-      const size_t column_bytes = column.n * column.nbytes;
-      u8* staged = own.take<u8>(column_bytes);
-      if (column_bytes != 0) {
-        BZ_HIP_CHECK(hipMemcpyAsync(staged, column.data, column_bytes, hipMemcpyHostToDevice, stream));
-      }
-      column.data = staged;
-    }
+    u64* d_vector;
+    u8 *d_evaluations, *d_workspace;
+    std::vector<sumcheck_column> on_device;
+    call.input(&d_vector, vector, static_cast<size_t>(32) * e.n);
+    call.output(&d_evaluations, evaluations, static_cast<size_t>(32) * e.num_columns);
+    call.scratch(&d_workspace, workspace_bytes);
+    call.columns(&on_device, e.columns, e.num_columns);
+    call.allocate();
     const column_evaluation staged{on_device.data(), e.num_columns, e.n};
-    evaluate_enqueue<E>(d_evaluations, d_vector, staged, d_workspace, workspace_bytes, stream);
-    BZ_HIP_CHECK(hipMemcpyAsync(evaluations, d_evaluations, evaluation_bytes, hipMemcpyDeviceToHost,
-                                stream));
-    BZ_HIP_CHECK(hipStreamSynchronize(stream));
-    own.release();
+    evaluate_enqueue<E>(d_evaluations, d_vector, staged, d_workspace, workspace_bytes,
+                        call.stream());
+    call.finish();
   });
 }
 } // namespace bz::proof

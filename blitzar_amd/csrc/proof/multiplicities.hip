@@ -52,6 +52,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "blitzar_amd/csrc/proof/host_call.h"
 #include "blitzar_amd/csrc/proof/sumcheck_columns.h"
 
 namespace bz::proof {
@@ -290,18 +291,8 @@ __global__ void __launch_bounds__(kCountThreads)
 }
 
 //--------------------------------------------------------------------------------------------------
-// checks
+// launch geometry
 //--------------------------------------------------------------------------------------------------
-struct byte_range {
-  const void* at;
-  u64 bytes;
-};
-bool overlap(const byte_range& a, const byte_range& b) {
-  if (a.at == nullptr || b.at == nullptr || a.bytes == 0 || b.bytes == 0) return false;
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.at), b0 = reinterpret_cast<uintptr_t>(b.at);
-  return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
 u32 blocks_for(u64 rows, u32 most) {
   const u64 blocks = (rows + kCountThreads - 1) / kCountThreads;
   return static_cast<u32>(std::min<u64>(most, std::max<u64>(blocks, 1)));
@@ -440,41 +431,24 @@ void count_multiplicities(api_state& st, u64* multiplicities, u64* misses, unsig
       return;
     }
     // the columns up at their own width, the device form, the results down
-    hipStream_t stream = st.primary().stream;
-    BZ_HIP_CHECK(hipSetDevice(st.primary().device));
-    const bool hashed = c.table.data != nullptr;
-    const size_t table_bytes = hashed ? c.table.n * c.table.nbytes : 0;
+    host_call call{st};
     const size_t lookup_bytes = c.lookups.n * c.lookups.nbytes;
-    const size_t out_bytes = 8 * c.table.n;
-    const size_t workspace_bytes = hashed ? multiplicity_workspace_bytes(c.table.n) : 0;
-    device_arena own;
-    own.reset(device_arena::padded(out_bytes) + device_arena::padded(8) +
-                  device_arena::padded(table_bytes) + device_arena::padded(lookup_bytes) +
-                  device_arena::padded(workspace_bytes) + 256,
-              stream);
-    u64* d_multiplicities = own.take<u64>(c.table.n);
-    u64* d_misses = own.take<u64>(1);
+    u64 *d_multiplicities, *d_misses;
     multiplicity_count staged = c;
-    if (hashed) {
-      u8* d_table = own.take<u8>(table_bytes);
-      BZ_HIP_CHECK(hipMemcpyAsync(d_table, c.table.data, table_bytes, hipMemcpyHostToDevice, stream));
-      staged.table.data = d_table;
-    }
-    u8* d_lookups = own.take<u8>(lookup_bytes);
-    if (lookup_bytes != 0) {
-      BZ_HIP_CHECK(
-          hipMemcpyAsync(d_lookups, c.lookups.data, lookup_bytes, hipMemcpyHostToDevice, stream));
-    }
-    staged.lookups.data = lookup_bytes != 0 ? d_lookups : nullptr;
-    void* workspace = hashed ? own.take<u8>(workspace_bytes) : nullptr;
-    count_enqueue<E>(d_multiplicities, d_misses, staged, workspace, stream);
-    BZ_HIP_CHECK(
-        hipMemcpyAsync(multiplicities, d_multiplicities, out_bytes, hipMemcpyDeviceToHost, stream));
+    void* workspace = nullptr;
+    // the misses are counted whether the caller asks for them or not
     u64 missed = 0;
-    BZ_HIP_CHECK(hipMemcpyAsync(&missed, d_misses, 8, hipMemcpyDeviceToHost, stream));
-    BZ_HIP_CHECK(hipStreamSynchronize(stream));
+    call.output(&d_multiplicities, multiplicities, 8 * c.table.n);
+    call.output(&d_misses, &missed, 8);
+    // a range table has no rows to upload and stays null; so do lookups of no rows
+    call.input(&staged.table.data, c.table.data, c.table.n * c.table.nbytes);
+    call.input(&staged.lookups.data, lookup_bytes != 0 ? c.lookups.data : nullptr, lookup_bytes);
+    // the hashed form alone has a workspace
+    if (c.table.data != nullptr) call.scratch(&workspace, multiplicity_workspace_bytes(c.table.n));
+    call.allocate();
+    count_enqueue<E>(d_multiplicities, d_misses, staged, workspace, call.stream());
+    call.finish();
     if (misses != nullptr) *misses = missed;
-    own.release();
   });
 }
 

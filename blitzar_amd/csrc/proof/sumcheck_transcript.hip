@@ -48,6 +48,7 @@
 #include <mutex>
 #include <vector>
 
+#include "blitzar_amd/csrc/proof/host_call.h"
 #include "blitzar_amd/csrc/proof/sumcheck_columns.h"
 #include "blitzar_amd/csrc/proof/sumcheck_protocol.h"
 #include "blitzar_amd/csrc/proof/transcript.h"
@@ -487,89 +488,23 @@ void prove_device_columns(const chain_target& to, const sumcheck_inputs& d,
   chain_rounds<E>(to, d, 1, d_table, mid, d_folded, d_partials, d_slot, d_products, d_terms);
 }
 
-// The GPU backend's forms on host operands, on the primary stream: the outputs, the transcript and
-// the chain's workspace in memory of the call's own, the transcript up, `chain(own, target)` --
-// which takes `input_bytes` more from `own`, uploads its inputs there and enqueues the device form
-// on them -- then the four results down, one synchronise
-template <class F, class Chain>
-void prove_uploaded(api_state& st, u8* polynomials, u8* evaluation_point, u8* mle_evaluations,
-                    u8* transcript, const sumcheck_inputs& d, bool columns, size_t input_bytes,
-                    Chain&& chain) {
-  const int device = st.primary().device;
-  hipStream_t stream = st.primary().stream;
-  BZ_HIP_CHECK(hipSetDevice(device));
+// What the GPU backend's forms on host operands declare alike before their tables or columns: the
+// three results (`mle_evaluations` may be null), the transcript, which goes up before the chain and
+// comes down after it, and the chain's workspace.  `to` is complete once `call` has allocated and
+// must stay where it is until then.
+template <class F>
+void declare_target(host_call& call, chain_target& to, void* polynomials, void* evaluation_point,
+                    void* mle_evaluations, void* transcript, const sumcheck_inputs& d,
+                    bool columns) {
   const u32 num_variables = variables_of(d.n);
-  const size_t poly_bytes = static_cast<size_t>(32) * (d.round_degree + 1) * num_variables;
-  const size_t point_bytes = static_cast<size_t>(32) * num_variables;
-  const size_t evaluation_bytes = static_cast<size_t>(32) * d.num_mles;
-  const chain_layout<F> layout{d, columns};
-  const size_t arena_bytes = input_bytes + device_arena::padded(poly_bytes) +
-                             device_arena::padded(point_bytes) +
-                             device_arena::padded(evaluation_bytes) + 256 + layout.total;
-  g_sumcheck_arena_bytes.store(arena_bytes);
-  device_arena own;
-  own.reset(arena_bytes, stream);
-  u8* d_polynomials = own.take<u8>(poly_bytes);
-  u8* d_point = own.take<u8>(point_bytes);
-  u8* d_evaluations = own.take<u8>(evaluation_bytes);
-  u8* d_transcript = own.take<u8>(sizeof(transcript_state));
-  u8* d_workspace = own.take<u8>(layout.total);
-  BZ_HIP_CHECK(hipMemcpyAsync(d_transcript, transcript, sizeof(transcript_state),
-                              hipMemcpyHostToDevice, stream));
-  chain(own, chain_target{d_polynomials, d_point,
-                          mle_evaluations != nullptr ? d_evaluations : nullptr, d_transcript,
-                          d_workspace, layout.total, stream});
-  BZ_HIP_CHECK(hipMemcpyAsync(polynomials, d_polynomials, poly_bytes, hipMemcpyDeviceToHost, stream));
-  BZ_HIP_CHECK(hipMemcpyAsync(evaluation_point, d_point, point_bytes, hipMemcpyDeviceToHost, stream));
-  if (mle_evaluations != nullptr) {
-    BZ_HIP_CHECK(hipMemcpyAsync(mle_evaluations, d_evaluations, evaluation_bytes,
-                                hipMemcpyDeviceToHost, stream));
-  }
-  BZ_HIP_CHECK(hipMemcpyAsync(transcript, d_transcript, sizeof(transcript_state),
-                              hipMemcpyDeviceToHost, stream));
-  BZ_HIP_CHECK(hipStreamSynchronize(stream));
-  own.release();
-}
-
-// host tables: uploaded as they are, converted on the device
-template <class E>
-void prove_uploaded_tables(api_state& st, u8* polynomials, u8* evaluation_point,
-                           u8* mle_evaluations, u8* transcript, const sumcheck_inputs& d) {
-  const size_t raw_bytes = static_cast<size_t>(E::element_bytes) * d.n * d.num_mles;
-  prove_uploaded<typename E::F>(
-      st, polynomials, evaluation_point, mle_evaluations, transcript, d, false,
-      device_arena::padded(raw_bytes), [&](device_arena& own, const chain_target& to) {
-        u8* d_raw = own.take<u8>(raw_bytes);
-        BZ_HIP_CHECK(hipMemcpyAsync(d_raw, d.mles, raw_bytes, hipMemcpyHostToDevice, to.stream));
-        sumcheck_inputs on_device = d;
-        on_device.mles = d_raw;
-        prove_device<E>(to, on_device);
-      });
-}
-
-// host columns: uploaded at their own width
-template <class E>
-void prove_uploaded_columns(api_state& st, u8* polynomials, u8* evaluation_point,
-                            u8* mle_evaluations, u8* transcript, const sumcheck_inputs& d,
-                            const sumcheck_column* columns) {
-  size_t column_bytes = 0;
-  for (u32 j = 0; j < d.num_mles; ++j) {
-    column_bytes += device_arena::padded(columns[j].n * columns[j].nbytes);
-  }
-  prove_uploaded<typename E::F>(
-      st, polynomials, evaluation_point, mle_evaluations, transcript, d, true, column_bytes,
-      [&](device_arena& own, const chain_target& to) {
-        std::vector<sumcheck_column> on_device(columns, columns + d.num_mles);
-        for (sumcheck_column& c : on_device) {
-          const size_t bytes = c.n * c.nbytes;
-          u8* staged = own.take<u8>(bytes);
-          if (bytes != 0) {
-            BZ_HIP_CHECK(hipMemcpyAsync(staged, c.data, bytes, hipMemcpyHostToDevice, to.stream));
-          }
-          c.data = staged;
-        }
-        prove_device_columns<E>(to, d, on_device.data());
-      });
+  to.workspace_bytes = chain_layout<F>{d, columns}.total;
+  to.stream = call.stream();
+  call.output(&to.polynomials, polynomials,
+              static_cast<size_t>(32) * (d.round_degree + 1) * num_variables);
+  call.output(&to.evaluation_point, evaluation_point, static_cast<size_t>(32) * num_variables);
+  call.output(&to.mle_evaluations, mle_evaluations, static_cast<size_t>(32) * d.num_mles);
+  call.in_out(&to.transcript, transcript, sizeof(transcript_state));
+  call.scratch(&to.workspace, to.workspace_bytes);
 }
 
 struct round_context {
@@ -637,9 +572,18 @@ void prove_sumcheck_transcript(api_state& st, void* polynomials, void* evaluatio
                      reinterpret_cast<void*>(&round_callback), &context);
       return;
     }
-    prove_uploaded_tables<decltype(elements)>(
-        st, static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
-        static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript), d);
+    // host tables: uploaded as they are, converted on the device
+    using E = decltype(elements);
+    host_call call{st};
+    chain_target to;
+    sumcheck_inputs on_device = d;
+    declare_target<typename E::F>(call, to, polynomials, evaluation_point, mle_evaluations,
+                                  transcript, d, false);
+    call.input(&on_device.mles, d.mles, static_cast<size_t>(E::element_bytes) * d.n * d.num_mles);
+    call.allocate();
+    g_sumcheck_arena_bytes.store(call.bytes());
+    prove_device<E>(to, on_device);
+    call.finish();
   });
 }
 
@@ -678,9 +622,18 @@ void prove_sumcheck_transcript_columns(api_state& st, void* polynomials, void* e
       return;
     }
     check_column_lengths(d, columns);
-    prove_uploaded_columns<decltype(elements)>(
-        st, static_cast<u8*>(polynomials), static_cast<u8*>(evaluation_point),
-        static_cast<u8*>(mle_evaluations), static_cast<u8*>(transcript), d, columns);
+    // host columns: uploaded at their own width
+    using E = decltype(elements);
+    host_call call{st};
+    chain_target to;
+    std::vector<sumcheck_column> on_device;
+    declare_target<typename E::F>(call, to, polynomials, evaluation_point, mle_evaluations,
+                                  transcript, d, true);
+    call.columns(&on_device, columns, d.num_mles);
+    call.allocate();
+    g_sumcheck_arena_bytes.store(call.bytes());
+    prove_device_columns<E>(to, d, on_device.data());
+    call.finish();
   });
 }
 

@@ -63,6 +63,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "blitzar_amd/csrc/proof/host_call.h"
 #include "blitzar_amd/csrc/proof/sumcheck_rows.h"
 
 namespace bz::proof {
@@ -552,15 +553,6 @@ __global__ void __launch_bounds__(kTileThreads)
 //--------------------------------------------------------------------------------------------------
 // checks
 //--------------------------------------------------------------------------------------------------
-struct byte_range {
-  const void* at;
-  u64 bytes;
-};
-bool overlap(const byte_range& a, const byte_range& b) {
-  if (a.at == nullptr || b.at == nullptr || a.bytes == 0 || b.bytes == 0) return false;
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.at), b0 = reinterpret_cast<uintptr_t>(b.at);
-  return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
 void check_disjoint(std::initializer_list<byte_range> outputs,
                     std::initializer_list<byte_range> inputs) {
   for (const byte_range& out : outputs) {
@@ -811,47 +803,6 @@ void quotients_enqueue(void* quotients, void* remainders, const univariate_openi
   BZ_HIP_CHECK(hipGetLastError());
   g_kernel_launches += 3;
 }
-
-// the operands of a blocking call on the GPU backend, uploaded to memory of the call's own
-struct staged_opening {
-  device_arena own;
-  univariate_opening on_device;
-  hipStream_t stream;
-  // `extra`: what the call takes from the arena beside the operands
-  staged_opening(api_state& st, const univariate_opening& o, bool with_folded, u32 point_rows,
-                 size_t extra) {
-    stream = st.primary().stream;
-    BZ_HIP_CHECK(hipSetDevice(st.primary().device));
-    const size_t polynomial_bytes = static_cast<size_t>(32) * o.n;
-    const size_t folded_bytes = static_cast<size_t>(32) * folded_rows(o.n, o.num_variables);
-    const size_t point_bytes = static_cast<size_t>(32) * point_rows;
-    own.reset(device_arena::padded(polynomial_bytes) + device_arena::padded(folded_bytes) +
-                  device_arena::padded(point_bytes) + extra,
-              stream);
-    u64* d_polynomial = own.take<u64>(4 * o.n);
-    u64* d_folded = own.take<u64>(folded_bytes / 8);
-    u8* d_points = own.take<u8>(point_bytes);
-    BZ_HIP_CHECK(hipMemcpyAsync(d_polynomial, o.polynomial, polynomial_bytes, hipMemcpyHostToDevice,
-                                stream));
-    if (with_folded && folded_bytes != 0) {
-      BZ_HIP_CHECK(hipMemcpyAsync(d_folded, o.folded, folded_bytes, hipMemcpyHostToDevice, stream));
-    }
-    BZ_HIP_CHECK(hipMemcpyAsync(d_points, o.points, point_bytes, hipMemcpyHostToDevice, stream));
-    on_device = o;
-    on_device.polynomial = d_polynomial;
-    on_device.folded = d_folded;
-    on_device.points = d_points;
-  }
-  void download(void* host, const void* device, size_t bytes) {
-    if (host != nullptr && bytes != 0) {
-      BZ_HIP_CHECK(hipMemcpyAsync(host, device, bytes, hipMemcpyDeviceToHost, stream));
-    }
-  }
-  void finish() {
-    BZ_HIP_CHECK(hipStreamSynchronize(stream));
-    own.release();
-  }
-};
 } // namespace
 
 std::vector<std::pair<u64, u64>> folded_layout(u64 n, u32 num_variables) {
@@ -883,18 +834,18 @@ void fold_polynomial(api_state& st, void* scalars, void* evaluation, unsigned fi
       return;
     }
     // the polynomial and the point up, the device form, the levels down
+    host_call call{st};
     const size_t folded_bytes = static_cast<size_t>(32) * folded_rows(o.n, o.num_variables);
-    staged_opening staged(st, o, false, o.num_variables,
-                          device_arena::padded(folded_bytes) + 256);
-    u64* d_scalars = staged.own.take<u64>(folded_bytes / 8);
-    u8* d_evaluation = staged.own.take<u8>(32);
-    fold_enqueue<E>(scalars != nullptr ? d_scalars : nullptr,
-                    evaluation != nullptr ? d_evaluation : nullptr, staged.on_device,
-                    staged.stream);
-    staged.download(o.folded, staged.on_device.folded, folded_bytes);
-    staged.download(scalars, d_scalars, folded_bytes);
-    staged.download(evaluation, d_evaluation, 32);
-    staged.finish();
+    univariate_opening on_device = o;
+    void *d_scalars, *d_evaluation;
+    call.input(&on_device.polynomial, o.polynomial, static_cast<size_t>(32) * o.n);
+    call.output(&on_device.folded, o.folded, folded_bytes);
+    call.input(&on_device.points, o.points, static_cast<size_t>(32) * o.num_variables);
+    call.output(&d_scalars, scalars, folded_bytes);
+    call.output(&d_evaluation, evaluation, 32);
+    call.allocate();
+    fold_enqueue<E>(d_scalars, d_evaluation, on_device, call.stream());
+    call.finish();
   });
 }
 
@@ -934,18 +885,21 @@ void evaluate_polynomials(api_state& st, void* evaluations, unsigned field_id,
       return;
     }
     // the levels and the points up, the device form, the evaluations down
-    const size_t evaluation_bytes = static_cast<size_t>(32) * o.num_variables * o.num_points;
+    host_call call{st};
     const size_t workspace_bytes =
         evaluate_layout<typename E::F>{o.n, o.num_variables, o.num_points}.total;
-    staged_opening staged(st, o, true, o.num_points,
-                          device_arena::padded(evaluation_bytes) +
-                              device_arena::padded(workspace_bytes));
-    u8* d_evaluations = staged.own.take<u8>(evaluation_bytes);
-    u8* d_workspace = staged.own.take<u8>(workspace_bytes);
-    evaluate_enqueue<E>(d_evaluations, staged.on_device, d_workspace, workspace_bytes,
-                        staged.stream);
-    staged.download(evaluations, d_evaluations, evaluation_bytes);
-    staged.finish();
+    univariate_opening on_device = o;
+    void *d_evaluations, *d_workspace;
+    call.input(&on_device.polynomial, o.polynomial, static_cast<size_t>(32) * o.n);
+    call.input(&on_device.folded, o.folded,
+               static_cast<size_t>(32) * folded_rows(o.n, o.num_variables));
+    call.input(&on_device.points, o.points, static_cast<size_t>(32) * o.num_points);
+    call.output(&d_evaluations, evaluations,
+                static_cast<size_t>(32) * o.num_variables * o.num_points);
+    call.scratch(&d_workspace, workspace_bytes);
+    call.allocate();
+    evaluate_enqueue<E>(d_evaluations, on_device, d_workspace, workspace_bytes, call.stream());
+    call.finish();
   });
 }
 
@@ -987,22 +941,22 @@ void batch_quotients(api_state& st, void* quotients, void* remainders, unsigned 
       return;
     }
     // the levels, the points and q up, the device form, the quotients and remainders down
-    const size_t quotient_bytes = static_cast<size_t>(32) * o.n * o.num_points;
-    const size_t remainder_bytes = static_cast<size_t>(32) * o.num_points;
+    host_call call{st};
     const size_t workspace_bytes = quotient_layout<typename E::F>{o.n, o.num_points}.total;
-    staged_opening staged(st, o, true, o.num_points,
-                          device_arena::padded(quotient_bytes) + 512 +
-                              device_arena::padded(workspace_bytes));
-    u64* d_quotients = staged.own.take<u64>(quotient_bytes / 8);
-    u8* d_remainders = staged.own.take<u8>(remainder_bytes);
-    u8* d_q = staged.own.take<u8>(32);
-    u8* d_workspace = staged.own.take<u8>(workspace_bytes);
-    BZ_HIP_CHECK(hipMemcpyAsync(d_q, q, 32, hipMemcpyHostToDevice, staged.stream));
-    quotients_enqueue<E>(d_quotients, remainders != nullptr ? d_remainders : nullptr,
-                         staged.on_device, d_q, d_workspace, workspace_bytes, staged.stream);
-    staged.download(quotients, d_quotients, quotient_bytes);
-    staged.download(remainders, d_remainders, remainder_bytes);
-    staged.finish();
+    univariate_opening on_device = o;
+    void *d_quotients, *d_remainders, *d_q, *d_workspace;
+    call.input(&on_device.polynomial, o.polynomial, static_cast<size_t>(32) * o.n);
+    call.input(&on_device.folded, o.folded,
+               static_cast<size_t>(32) * folded_rows(o.n, o.num_variables));
+    call.input(&on_device.points, o.points, static_cast<size_t>(32) * o.num_points);
+    call.output(&d_quotients, quotients, static_cast<size_t>(32) * o.n * o.num_points);
+    call.output(&d_remainders, remainders, static_cast<size_t>(32) * o.num_points);
+    call.input(&d_q, q, 32);
+    call.scratch(&d_workspace, workspace_bytes);
+    call.allocate();
+    quotients_enqueue<E>(d_quotients, d_remainders, on_device, d_q, d_workspace, workspace_bytes,
+                         call.stream());
+    call.finish();
   });
 }
 } // namespace bz::proof
