@@ -242,6 +242,15 @@ def load():
         lib.bzamd_count_multiplicities_device.restype = None
         lib.bzamd_multiplicity_first_slot.argtypes = [cu, vp, u64]
         lib.bzamd_multiplicity_first_slot.restype = u64
+    if hasattr(lib, "bzamd_decompose_words_device"):
+        lib.bzamd_decompose_words.argtypes = [vp, vp, vp, cu, vp]
+        lib.bzamd_decompose_words.restype = None
+        lib.bzamd_decompose_words_device.argtypes = [vp, vp, vp, cu, vp, vp]
+        lib.bzamd_decompose_words_device.restype = None
+        lib.bzamd_map_words.argtypes = [vp, vp]
+        lib.bzamd_map_words.restype = None
+        lib.bzamd_map_words_device.argtypes = [vp, vp, vp]
+        lib.bzamd_map_words_device.restype = None
     if hasattr(lib, "bzamd_evaluate_columns_device"):
         lib.bzamd_evaluate_columns.argtypes = [vp, cu, vp, vp]
         lib.bzamd_evaluate_columns.restype = None
@@ -1053,6 +1062,77 @@ def count_multiplicities_device(field_id, multiplicities_ptr, misses_ptr, table,
         None if misses_ptr is None else int(misses_ptr), field_id, ctypes.byref(c),
         None if workspace_ptr is None else int(workspace_ptr), workspace_bytes,
         None if stream is None else ctypes.c_void_p(int(stream)))
+
+
+class bzamd_word_decomposition(ctypes.Structure):
+    _fields_ = [("column", sxt_sequence_descriptor), ("shift", ctypes.c_void_p),
+                ("num_words", ctypes.c_uint), ("plane_stride", ctypes.c_uint64)]
+
+
+class bzamd_word_map(ctypes.Structure):
+    _fields_ = [("words", ctypes.c_void_p), ("table", ctypes.c_void_p),
+                ("num_planes", ctypes.c_uint), ("n", ctypes.c_uint64),
+                ("plane_stride", ctypes.c_uint64), ("mapped_stride", ctypes.c_uint64)]
+
+
+def decompose_words(field_id, column, num_words, shift=None, want_words=True):
+    """bzamd_decompose_words (host operands, either backend).  column: as in combine_columns (an
+    array or an (array, is_signed) pair); shift: uint8 [32] in element form (None: 0)
+    -> (words uint8 [num_words, n], counts uint64 [256], overflow): words[k, i] is byte k of the
+    key of shift + column[i]; want_words False: a null pointer, words is None"""
+    descs, keep = make_descriptors(_column_pairs([column]))
+    n = int(descs[0].n)
+    if shift is not None:
+        shift = np.ascontiguousarray(shift, dtype=np.uint8)
+    words = np.zeros((num_words, max(n, 1)), dtype=np.uint8) if want_words else None
+    counts = np.zeros(256, dtype=np.uint64)
+    overflow = ctypes.c_uint64(0)
+    d = bzamd_word_decomposition(descs[0], None if shift is None else shift.ctypes.data, num_words,
+                                 max(n, 1))
+    load().bzamd_decompose_words(_ptr(words), _ptr(counts), ctypes.byref(overflow), field_id,
+                                 ctypes.byref(d))
+    del keep
+    return (None if words is None else words[:, :n]), counts, int(overflow.value)
+
+
+def decompose_words_device(field_id, words_ptr, counts_ptr, overflow_ptr, column, num_words,
+                           plane_stride, shift_ptr=None, stream=None):
+    """bzamd_decompose_words_device: enqueue only, two kernel launches.  column: (device_ptr, rows,
+    nbytes, signed); every *_ptr is memory of the current device as an integer (None: a null
+    pointer); `stream` a hipStream_t as an integer (None: the default stream)."""
+    ptr, rows, nbytes, signed = column
+    d = bzamd_word_decomposition(
+        sxt_sequence_descriptor(nbytes, rows, None if ptr is None else int(ptr), 1 if signed else 0),
+        None if shift_ptr is None else int(shift_ptr), num_words, plane_stride)
+    load().bzamd_decompose_words_device(
+        None if words_ptr is None else int(words_ptr),
+        None if counts_ptr is None else int(counts_ptr),
+        None if overflow_ptr is None else int(overflow_ptr), field_id, ctypes.byref(d),
+        None if stream is None else ctypes.c_void_p(int(stream)))
+
+
+def map_words(words, table):
+    """bzamd_map_words (host operands, either backend).  words: uint8 [num_planes, n]; table:
+    uint8 [256, 32] -> uint8 [num_planes, n, 32]: mapped[k, i] = table[words[k, i]]"""
+    words = np.ascontiguousarray(words, dtype=np.uint8)
+    table = np.ascontiguousarray(table, dtype=np.uint8)
+    num_planes, n = words.shape
+    mapped = np.zeros((num_planes, n, 32), dtype=np.uint8)
+    m = bzamd_word_map(words.ctypes.data, table.ctypes.data, num_planes, n, n, 32 * n)
+    load().bzamd_map_words(_ptr(mapped), ctypes.byref(m))
+    return mapped
+
+
+def map_words_device(mapped_ptr, words_ptr, table_ptr, num_planes, n, plane_stride, mapped_stride,
+                     stream=None):
+    """bzamd_map_words_device: enqueue only, one kernel launch.  Every *_ptr is memory of the
+    current device as an integer (None: a null pointer); `stream` a hipStream_t as an integer
+    (None: the default stream)."""
+    m = bzamd_word_map(None if words_ptr is None else int(words_ptr),
+                       None if table_ptr is None else int(table_ptr), num_planes, n, plane_stride,
+                       mapped_stride)
+    load().bzamd_map_words_device(None if mapped_ptr is None else int(mapped_ptr), ctypes.byref(m),
+                                  None if stream is None else ctypes.c_void_p(int(stream)))
 
 
 class bzamd_column_evaluation(ctypes.Structure):

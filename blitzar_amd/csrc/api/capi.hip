@@ -32,6 +32,7 @@
 #include "blitzar_amd/csrc/proof/sumcheck_transcript.h"
 #include "blitzar_amd/csrc/proof/transcript.h"
 #include "blitzar_amd/csrc/proof/verify_opening.h"
+#include "blitzar_amd/csrc/proof/word_columns.h"
 #include "include/blitzar_amd.h"
 
 using namespace bz;
@@ -2195,6 +2196,57 @@ void bzamd_count_multiplicities_device(void* multiplicities, void* misses, unsig
 uint64_t bzamd_multiplicity_first_slot(unsigned field_id, const void* element,
                                        uint64_t table_rows) {
   return proof::multiplicity_first_slot(field_id, element, table_rows);
+}
+
+namespace {
+// the decomposition's column, checked as in prove_sumcheck_columns_entry
+proof::word_decomposition decomposition_form(const char* name, const void* words,
+                                             const void* counts, const void* overflow,
+                                             const struct bzamd_word_decomposition* d) {
+  check_arguments(name, d != nullptr &&
+                            (words != nullptr || counts != nullptr || overflow != nullptr));
+  return {checked_sumcheck_columns(&d->column, 1)[0], d->shift, d->num_words, d->plane_stride};
+}
+proof::word_map map_form(const char* name, const void* mapped, const struct bzamd_word_map* m) {
+  check_arguments(name, mapped != nullptr && m != nullptr && m->words != nullptr &&
+                            m->table != nullptr);
+  return {m->words, m->table, m->num_planes, m->n, m->plane_stride, m->mapped_stride};
+}
+} // namespace
+
+// the word columns of a range check (proof/word_columns.hip).  Both forms check their arguments
+// before they ask for the backend
+void bzamd_decompose_words(void* words, uint64_t* counts, uint64_t* overflow, unsigned field_id,
+                           const struct bzamd_word_decomposition* d) {
+  const proof::word_decomposition decomposition =
+      decomposition_form("bzamd_decompose_words", words, counts, overflow, d);
+  proof::check_word_decomposition(words, counts, overflow, field_id, decomposition);
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::decompose_words(st, words, counts, overflow, field_id, decomposition);
+}
+
+void bzamd_decompose_words_device(void* words, void* counts, void* overflow, unsigned field_id,
+                                  const struct bzamd_word_decomposition* d, void* stream) {
+  const proof::word_decomposition decomposition =
+      decomposition_form("bzamd_decompose_words_device", words, counts, overflow, d);
+  proof::check_word_decomposition(words, counts, overflow, field_id, decomposition);
+  proof::decompose_words_device(words, static_cast<u64*>(counts), static_cast<u64*>(overflow),
+                                field_id, decomposition, device_form(stream).stream);
+}
+
+void bzamd_map_words(void* mapped, const struct bzamd_word_map* m) {
+  const proof::word_map map = map_form("bzamd_map_words", mapped, m);
+  proof::check_word_map(mapped, map);
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::map_words(st, mapped, map);
+}
+
+void bzamd_map_words_device(void* mapped, const struct bzamd_word_map* m, void* stream) {
+  const proof::word_map map = map_form("bzamd_map_words_device", mapped, m);
+  proof::check_word_map(mapped, map);
+  proof::map_words_device(mapped, map, device_form(stream).stream);
 }
 
 namespace {

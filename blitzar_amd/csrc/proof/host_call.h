@@ -1,7 +1,8 @@
 // What the proof operations on host operands share (proof/column_inverse.hip, multiplicities.hip,
-// mle_opening.hip, univariate_opening.hip, sumcheck_transcript.hip): the overlap test of their
-// argument checks, and the staging of a blocking call on the GPU backend.  Such a call declares its
-// buffers, allocates once, enqueues its device form on the staged pointers and finishes:
+// word_columns.hip, mle_opening.hip, univariate_opening.hip, sumcheck_transcript.hip): the overlap
+// test of their argument checks, and the staging of a blocking call on the GPU backend.  Such a
+// call declares its buffers, allocates once, enqueues its device form on the staged pointers and
+// finishes:
 //
 //   host_call call{st};
 //   call.input(&d_point, point, point_bytes);

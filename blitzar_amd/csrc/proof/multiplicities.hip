@@ -43,17 +43,14 @@
 // wave_adder.  One- and two-byte columns are read 16 bytes a lane where the address allows
 // (the rows before the first and after the last whole 16 bytes go the general way).
 //
-// Key extraction reuses load_magnitude of proof/sumcheck_columns.h: a non-negative row below 32
-// bytes is its own key (below 2^248 < p); a negative row takes one subtraction; a 32-byte row one
-// reduction, and in field 1 one product by 2^5 (x 2^256 2^5 / 2^261 = x) to leave Montgomery form.
+// Key extraction is key_of of proof/column_key.h, shared with proof/word_columns.hip.
 // No scratch memory in any kernel (tests/test_multiplicities.py reads the compiler's report).
 #include "blitzar_amd/csrc/proof/multiplicities.h"
 
-#include <type_traits>
 #include <vector>
 
+#include "blitzar_amd/csrc/proof/column_key.h"
 #include "blitzar_amd/csrc/proof/host_call.h"
-#include "blitzar_amd/csrc/proof/sumcheck_columns.h"
 
 namespace bz::proof {
 namespace {
@@ -62,24 +59,6 @@ constexpr u32 kCountThreads = 256;
 constexpr u32 kCountBlocks = 2048;
 constexpr u32 kLdsBins = 4096;        // 16 KB of u32 bins
 constexpr u32 kLdsBlocks = 1024;    // each adds its non-zero bins at the end
-
-template <class E> BZ_HD lookup_key key_of(const column_view& c, u64 i) {
-  using F = typename E::F;
-  lookup_key key = {{0, 0, 0, 0}};
-  const bool negative = load_magnitude(key.w, c, i);
-  if (c.nbytes < E::element_bytes && !negative) return key;
-  typename F::fe v = F::reduce(F::from_words(key.w));
-  if (negative) v = fneg<F>(v);
-  if constexpr (std::is_same_v<E, grumpkin_elements>) {
-    if (c.nbytes == E::element_bytes) {
-      typename F::fe c5 = F::zero();
-      c5.v[0] = 1u << (F::LB * F::N - 256);
-      v = F::mul(v, c5);
-    }
-  }
-  F::to_words(key.w, F::canonical(v));
-  return key;
-}
 
 //--------------------------------------------------------------------------------------------------
 // device kernels

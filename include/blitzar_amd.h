@@ -749,6 +749,81 @@ void bzamd_count_multiplicities_device(void* multiplicities, void* misses, unsig
  * element.  The hash is NOT part of the ABI and may change between versions. */
 uint64_t bzamd_multiplicity_first_slot(unsigned field_id, const void* element, uint64_t table_rows);
 
+/* The word columns of a range check.  A value is in range when its byte words are: every word is
+ * looked up in the table 0 .. 255, and the prover commits to the word columns, the 256 word counts
+ * and one inverse column 1 / (alpha + word) per word column.
+ *   key(i) = the canonical integer in [0, p) of shift + column[i],   i < n = column.n.
+ * The column is the MSM's / sumcheck's descriptor and means what it means in
+ * bzamd_count_multiplicities, validated by the same rule: element_nbytes 1 .. 31 little-endian
+ * integers, two's complement when is_signed (up to 16 bytes; a negative row is p - |x|);
+ * element_nbytes 32 the field's elements, unreduced values included (x and x + p have one key),
+ * Montgomery words in field 1; data at any address.  `shift` (NULL: 0; else 32 bytes in element
+ * form at any address, may be unreduced) lets a signed column be checked without a 32-byte
+ * intermediate: with shift = 2^63 every i64 has a key below 2^64.
+ *   words:    num_words planes of n bytes, words[k * plane_stride + i] = byte k of key(i),
+ *             k < num_words, i < n.  The planes may start at any address; bytes between n and
+ *             plane_stride are not written.  Each plane is an ordinary 1-byte unsigned column for
+ *             bzamd_msm_device, the sumcheck provers and every columns call.
+ *   counts:   256 x 8 bytes, little-endian uint64_t, 8-byte aligned: counts[v] = the number of
+ *             pairs (k, i), k < num_words, i < n, whose byte is v; their sum is num_words * n.
+ *             What the columns calls read as an 8-byte unsigned column of 256 rows: the
+ *             multiplicity column of the lookup of ALL planes in the table 0 .. 255.
+ *   overflow: one uint64_t, 8-byte aligned: the number of rows with key(i) >= 2^(8 num_words),
+ *             always 0 for num_words = 32.  Words of those rows are the low bytes all the same.
+ *             The range check holds exactly when overflow = 0.
+ * words, counts and overflow may each be NULL, not all three.  No input is written.
+ * Limits: 0 <= n <= 2^30 (n = 0 with data = NULL writes 256 zeros and overflow = 0),
+ * 1 <= num_words <= 32, plane_stride >= n, field_id 0 or 1.  Aborts, before anything is launched: a
+ * null d, all outputs null, a bad descriptor, a limit exceeded, plane_stride < n, a misaligned
+ * counts or overflow, an output that overlaps an input or another output (the planes' range is
+ * (num_words - 1) * plane_stride + n bytes), an unsupported field id, the device form on the cpu
+ * backend. */
+struct bzamd_word_decomposition {
+  struct sxt_sequence_descriptor column; /* n = column.n rows */
+  const void* shift;                     /* may be NULL: 0; else 32 bytes, element form */
+  unsigned num_words;                    /* 1 .. 32 */
+  uint64_t plane_stride;                 /* bytes from plane k to plane k + 1; >= n */
+};
+/* HOST operands (column.data included), blocking, cpu and gpu backends.  The cpu backend goes row
+ * by row; the gpu backend uploads the column at its own width, runs the device form on memory of
+ * the call's own, synchronises once and downloads the outputs plane by plane. */
+void bzamd_decompose_words(void* words, uint64_t* counts, uint64_t* overflow, unsigned field_id,
+                           const struct bzamd_word_decomposition* d);
+/* DEVICE pointers on the current HIP device: words, counts, overflow, shift and column.data (read
+ * in stream order, never written).  HOST: the struct, which is read before the call returns.  gpu
+ * backend only (anything else aborts).  The call only enqueues on `stream`: no synchronise, no
+ * allocation, no callback, no workspace.  TWO kernel launches, whatever n, num_words and the data
+ * are. */
+void bzamd_decompose_words_device(void* words, void* counts, void* overflow, unsigned field_id,
+                                  const struct bzamd_word_decomposition* d, void* stream);
+
+/* The columns a word plane maps to through a table of 256 rows of 32 bytes:
+ *   mapped[k * mapped_stride + 32 i ..+32] = table[words_k[i]],   k < num_planes, i < n,
+ * with words_k[i] = words[k * plane_stride + i].  A byte copy: it works for either field and
+ * either form.  With the `inverses` table of bzamd_invert_columns_device over the one-byte column
+ * 0 .. 255 and shift = alpha, the outputs are the inverse-word columns 1 / (alpha + word) in
+ * element form, for the price of moving their bytes instead of one field inversion a row; with its
+ * `scalars` table they are what bzamd_msm_device reads as 32-byte columns.
+ * 1 <= n <= 2^30, 1 <= num_planes <= 32, plane_stride >= n, mapped_stride >= 32 n and a multiple
+ * of 8, `mapped` 8-byte aligned; words and table at any address.  Aborts, before anything is
+ * launched: a null mapped, m, words or table, a limit exceeded, a bad stride, a misaligned mapped,
+ * an output that overlaps an input (the mapped range is (num_planes - 1) * mapped_stride + 32 n
+ * bytes), the device form on the cpu backend.  No input is written. */
+struct bzamd_word_map {
+  const void* words;        /* num_planes planes of n bytes, plane k at words + k * plane_stride */
+  const void* table;        /* 256 x 32 bytes */
+  unsigned num_planes;      /* 1 .. 32 */
+  uint64_t n, plane_stride; /* plane_stride >= n */
+  uint64_t mapped_stride;   /* bytes from mapped column k to k + 1; >= 32 n, a multiple of 8 */
+};
+/* HOST operands, blocking, cpu and gpu backends (the gpu backend uploads the planes and the table,
+ * runs the device form, synchronises once and downloads the columns one by one). */
+void bzamd_map_words(void* mapped, const struct bzamd_word_map* m);
+/* DEVICE pointers on the current HIP device: mapped, words and table (read in stream order, never
+ * written).  HOST: the struct.  gpu backend only.  Enqueue only: no synchronise, no allocation, no
+ * callback, no workspace.  ONE kernel launch, whatever n, num_planes and the data are. */
+void bzamd_map_words_device(void* mapped, const struct bzamd_word_map* m, void* stream);
+
 /* The MLE evaluations of typed columns, given the evaluation vector of the point:
  *   evaluations[j] = sum_{i < columns[j].n} column_j[i] * vector[i],
  * num_columns x 32 bytes, written canonical (no alignment needed).  With the vector of
