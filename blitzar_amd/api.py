@@ -242,6 +242,13 @@ def load():
         lib.bzamd_count_multiplicities_device.restype = None
         lib.bzamd_multiplicity_first_slot.argtypes = [cu, vp, u64]
         lib.bzamd_multiplicity_first_slot.restype = u64
+    if hasattr(lib, "bzamd_sum_by_key_device"):
+        lib.bzamd_sum_by_key_workspace_bytes.argtypes = [u64, cu]
+        lib.bzamd_sum_by_key_workspace_bytes.restype = u64
+        lib.bzamd_sum_by_key.argtypes = [vp, vp, vp, vp, vp, cu, vp]
+        lib.bzamd_sum_by_key.restype = None
+        lib.bzamd_sum_by_key_device.argtypes = [vp, vp, vp, vp, vp, cu, vp, vp, u64, vp]
+        lib.bzamd_sum_by_key_device.restype = None
     if hasattr(lib, "bzamd_decompose_words_device"):
         lib.bzamd_decompose_words.argtypes = [vp, vp, vp, cu, vp]
         lib.bzamd_decompose_words.restype = None
@@ -1060,6 +1067,70 @@ def count_multiplicities_device(field_id, multiplicities_ptr, misses_ptr, table,
     load().bzamd_count_multiplicities_device(
         None if multiplicities_ptr is None else int(multiplicities_ptr),
         None if misses_ptr is None else int(misses_ptr), field_id, ctypes.byref(c),
+        None if workspace_ptr is None else int(workspace_ptr), workspace_bytes,
+        None if stream is None else ctypes.c_void_p(int(stream)))
+
+
+class bzamd_key_sums(ctypes.Structure):
+    _fields_ = [("table", sxt_sequence_descriptor), ("lookups", sxt_sequence_descriptor),
+                ("values", ctypes.POINTER(sxt_sequence_descriptor)),
+                ("num_values", ctypes.c_uint)]
+
+
+def sum_by_key_workspace_bytes(table_rows, num_values):
+    """bzamd_sum_by_key_workspace_bytes: no backend needed; 0 outside the limits"""
+    return load().bzamd_sum_by_key_workspace_bytes(table_rows, num_values)
+
+
+def sum_by_key(field_id, table, lookups, values=(), want=("sums", "scalars", "counts", "misses",
+                                                          "matches")):
+    """bzamd_sum_by_key (host operands, either backend).  table, lookups: as in
+    count_multiplicities (table may be (None, m): the range table); values: value columns as in
+    combine_columns, at most lookups' rows each; want: the outputs asked for, the others are null
+    pointers -> a dict of those: sums, scalars uint8 [num_values, m, 32]; counts uint64 [m];
+    misses an int; matches uint32 [n]"""
+    if isinstance(table, tuple) and table[0] is None:
+        table_desc, keep_table = sxt_sequence_descriptor(8, int(table[1]), None, 0), None
+    else:
+        descs, keep_table = make_descriptors(_column_pairs([table]))
+        table_desc = descs[0]
+    lookup_descs, keep_lookups = make_descriptors(_column_pairs([lookups]))
+    value_descs, keep_values = make_descriptors(_column_pairs(values))
+    m, n, count = int(table_desc.n), int(lookup_descs[0].n), len(keep_values)
+    out = {"sums": np.zeros((count, max(m, 1), 32), dtype=np.uint8),
+           "scalars": np.zeros((count, max(m, 1), 32), dtype=np.uint8),
+           "counts": np.zeros(max(m, 1), dtype=np.uint64),
+           "misses": np.zeros(1, dtype=np.uint64),
+           "matches": np.zeros(max(n, 1), dtype=np.uint32)}
+    out = {name: array for name, array in out.items() if name in want}
+    k = bzamd_key_sums(table_desc, lookup_descs[0], value_descs if count else None, count)
+    load().bzamd_sum_by_key(*(_ptr(out.get(name)) for name in ("sums", "scalars", "counts",
+                                                               "misses", "matches")),
+                            field_id, ctypes.byref(k))
+    del keep_table, keep_lookups, keep_values
+    shaped = {"sums": lambda a: a[:, :m], "scalars": lambda a: a[:, :m], "counts": lambda a: a[:m],
+              "misses": lambda a: int(a[0]), "matches": lambda a: a[:n]}
+    return {name: shaped[name](array) for name, array in out.items()}
+
+
+def sum_by_key_device(field_id, sums_ptr, scalars_ptr, counts_ptr, misses_ptr, matches_ptr, table,
+                      lookups, values, workspace_ptr, workspace_bytes, stream=None):
+    """bzamd_sum_by_key_device: enqueue only, four kernel launches (the range table: three).
+    table, lookups: one (device_ptr, rows, nbytes, signed) each; a table with device_ptr None is
+    the range table 0 .. rows - 1; values: a list of such tuples; every *_ptr is memory of the
+    current device as an integer (None: a null pointer); `stream` a hipStream_t as an integer
+    (None: the default stream)."""
+    def descriptor(column):
+        ptr, rows, nbytes, signed = column
+        return sxt_sequence_descriptor(nbytes, rows, None if ptr is None else int(ptr),
+                                       1 if signed else 0)
+    value_descs, count = _device_descriptors(values)
+    k = bzamd_key_sums(descriptor(table), descriptor(lookups), value_descs if count else None,
+                       count)
+    pointers = [None if p is None else int(p)
+                for p in (sums_ptr, scalars_ptr, counts_ptr, misses_ptr, matches_ptr)]
+    load().bzamd_sum_by_key_device(
+        *pointers, field_id, ctypes.byref(k),
         None if workspace_ptr is None else int(workspace_ptr), workspace_bytes,
         None if stream is None else ctypes.c_void_p(int(stream)))
 

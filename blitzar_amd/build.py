@@ -38,6 +38,7 @@ SOURCES = [
     "proof/mle_opening.hip",
     "proof/column_inverse.hip",
     "proof/multiplicities.hip",
+    "proof/key_sums.hip",
     "proof/word_columns.hip",
     "proof/univariate_opening.hip",
     "proof/verify_opening.hip",

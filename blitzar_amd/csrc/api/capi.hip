@@ -25,6 +25,7 @@
 #include "blitzar_amd/csrc/fixed/handle.h"
 #include "blitzar_amd/csrc/proof/inner_product.h"
 #include "blitzar_amd/csrc/proof/column_inverse.h"
+#include "blitzar_amd/csrc/proof/key_sums.h"
 #include "blitzar_amd/csrc/proof/mle_opening.h"
 #include "blitzar_amd/csrc/proof/multiplicities.h"
 #include "blitzar_amd/csrc/proof/univariate_opening.h"
@@ -2196,6 +2197,57 @@ void bzamd_count_multiplicities_device(void* multiplicities, void* misses, unsig
 uint64_t bzamd_multiplicity_first_slot(unsigned field_id, const void* element,
                                        uint64_t table_rows) {
   return proof::multiplicity_first_slot(field_id, element, table_rows);
+}
+
+namespace {
+// the columns of the sums by key: table and lookups as in multiplicity_form_columns, the value
+// columns checked as in prove_sumcheck_columns_entry.  `values` keeps them alive
+proof::key_sums key_sum_form_columns(const char* name, const struct bzamd_key_sums* k,
+                                     std::vector<proof::sumcheck_column>& values) {
+  check_arguments(name, k != nullptr && (k->num_values == 0 || k->values != nullptr));
+  BZ_RELEASE_ASSERT(k->num_values <= proof::kMaxKeySumValues,
+                    "the sums by key need num_values <= 8");
+  proof::key_sums sums;
+  if (k->table.data == nullptr) {
+    BZ_RELEASE_ASSERT(k->table.element_nbytes == 8 && !k->table.is_signed,
+                      "a NULL table is the range table: element_nbytes 8, unsigned");
+    sums.table = proof::sumcheck_column{nullptr, k->table.n, 8, false};
+  } else {
+    sums.table = checked_sumcheck_columns(&k->table, 1)[0];
+  }
+  sums.lookups = checked_sumcheck_columns(&k->lookups, 1)[0];
+  values = checked_sumcheck_columns(k->values, k->num_values);
+  sums.values = values.data();
+  sums.num_values = k->num_values;
+  return sums;
+}
+} // namespace
+
+// sums of value columns by key (proof/key_sums.hip).  Both forms check their arguments before they
+// ask for the backend
+uint64_t bzamd_sum_by_key_workspace_bytes(uint64_t table_rows, unsigned num_values) {
+  return proof::key_sum_workspace_bytes(table_rows, num_values);
+}
+
+void bzamd_sum_by_key(void* sums, void* scalars, void* counts, uint64_t* misses, void* matches,
+                      unsigned field_id, const struct bzamd_key_sums* k) {
+  std::vector<proof::sumcheck_column> values;
+  const proof::key_sums key_sums = key_sum_form_columns("bzamd_sum_by_key", k, values);
+  const proof::key_sum_outputs out{sums, scalars, counts, misses, matches};
+  proof::check_key_sums(out, field_id, key_sums, nullptr, 0, false);
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::sum_by_key(st, out, field_id, key_sums);
+}
+
+void bzamd_sum_by_key_device(void* sums, void* scalars, void* counts, void* misses, void* matches,
+                             unsigned field_id, const struct bzamd_key_sums* k, void* workspace,
+                             uint64_t workspace_bytes, void* stream) {
+  std::vector<proof::sumcheck_column> values;
+  const proof::key_sums key_sums = key_sum_form_columns("bzamd_sum_by_key_device", k, values);
+  const proof::key_sum_outputs out{sums, scalars, counts, misses, matches};
+  proof::check_key_sums(out, field_id, key_sums, workspace, workspace_bytes, true);
+  proof::sum_by_key_device(out, field_id, key_sums, workspace, device_form(stream).stream);
 }
 
 namespace {

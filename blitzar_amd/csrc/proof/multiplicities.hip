@@ -43,20 +43,19 @@
 // wave_adder.  One- and two-byte columns are read 16 bytes a lane where the address allows
 // (the rows before the first and after the last whole 16 bytes go the general way).
 //
+// The clear of the slots, k_insert_rows, the find loop, wave_adder and the launch geometry are in
+// proof/key_table.h, shared with proof/key_sums.hip (each unit instantiates its own kernels).
 // Key extraction is key_of of proof/column_key.h, shared with proof/word_columns.hip.
 // No scratch memory in any kernel (tests/test_multiplicities.py reads the compiler's report).
 #include "blitzar_amd/csrc/proof/multiplicities.h"
 
 #include <vector>
 
-#include "blitzar_amd/csrc/proof/column_key.h"
 #include "blitzar_amd/csrc/proof/host_call.h"
+#include "blitzar_amd/csrc/proof/key_table.h"
 
 namespace bz::proof {
 namespace {
-constexpr u32 kCountThreads = 256;
-// 8 workgroups of 4 wavefronts per CU: the probes are dependent loads, more wavefronts hide more
-constexpr u32 kCountBlocks = 2048;
 constexpr u32 kLdsBins = 4096;        // 16 KB of u32 bins
 constexpr u32 kLdsBlocks = 1024;    // each adds its non-zero bins at the end
 
@@ -68,67 +67,10 @@ __global__ void __launch_bounds__(kCountThreads)
                            u64* misses) {
   const u64 stride = static_cast<u64>(gridDim.x) * kCountThreads;
   const u64 first = static_cast<u64>(blockIdx.x) * kCountThreads + threadIdx.x;
-  for (u64 s = first; s < slots; s += stride) slot_rows[s] = kEmptySlot;
+  clear_slots(slot_rows, slots, first, stride);
   for (u64 t = first; t < table_rows; t += stride) multiplicities[t] = 0;
   if (first == 0 && misses != nullptr) *misses = 0;
 }
-
-template <class E>
-__global__ void __launch_bounds__(kCountThreads)
-    k_insert_rows(u32* slot_rows, u64 slots, const column_view table) {
-  const u64 stride = static_cast<u64>(gridDim.x) * kCountThreads;
-  for (u64 t = static_cast<u64>(blockIdx.x) * kCountThreads + threadIdx.x; t < table.n;
-       t += stride) {
-    const lookup_key key = key_of<E>(table, t);
-    const u32 mine = static_cast<u32>(t);
-    u64 slot = first_slot(key, slots);
-    for (u64 step = 0; step < slots; ++step, slot = (slot + 1) & (slots - 1)) {
-      u32 row = __hip_atomic_load(slot_rows + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (row == kEmptySlot) {
-        row = atomicCAS(slot_rows + slot, kEmptySlot, mine);
-        if (row == kEmptySlot) break;
-      }
-      // a row of the table (the clear and this kernel write nothing else); guarded all the same
-      if (row >= table.n) break;
-      if (same_key(key_of<E>(table, row), key)) {
-        if (mine < row) atomicMin(slot_rows + slot, mine);
-        break;
-      }
-    }
-  }
-}
-
-// One wavefront's adds to `multiplicities`, aggregated: add() takes a row per lane, and while lanes
-// remain it broadcasts the first remaining lane's row, ballots the lanes that share it and counts
-// them.  The count is not added at once but kept, with its row, in two wave-uniform registers, and
-// added by one lane when the next row differs or at flush(): runs of one row, within a wavefront and
-// from one turn of its loop to the next, cost one atomic.  Called by all 64 lanes together
-// (wave-uniform control flow around every call); a wavefront sees fewer than 2^32 rows
-struct wave_adder {
-  u32 row = kEmptySlot, count = 0;
-  __device__ __forceinline__ void flush(u64* multiplicities) {
-    if (count != 0 && __lane_id() == 0) {
-      (void)__hip_atomic_fetch_add(multiplicities + row, static_cast<u64>(count), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-    }
-    count = 0;
-  }
-  __device__ __forceinline__ void add(u64* multiplicities, u32 lane_row, bool hit) {
-    u64 remaining = __ballot(hit);
-    while (remaining != 0) {
-      const u32 leader = static_cast<u32>(__ffsll(static_cast<long long>(remaining))) - 1;
-      const u32 leader_row = static_cast<u32>(
-          __builtin_amdgcn_readlane(static_cast<int>(lane_row), static_cast<int>(leader)));
-      const u64 same = __ballot(hit && lane_row == leader_row);
-      if (leader_row != row) {
-        flush(multiplicities);
-        row = leader_row;
-      }
-      count += static_cast<u32>(__popcll(same));
-      remaining &= ~same;
-    }
-  }
-};
 
 // kLds (tables of at most kLdsBins rows): hits go to 32-bit bins in LDS, one per table row, and the
 // workgroup adds its non-zero bins at the end (it sees fewer than 2^32 rows)
@@ -148,18 +90,7 @@ __global__ void __launch_bounds__(kCountThreads)
     const u64 i = base + threadIdx.x;
     const bool active = i < lookups.n;
     u32 found = kEmptySlot;
-    if (active) {
-      const lookup_key key = key_of<E>(lookups, i);
-      u64 slot = first_slot(key, slots);
-      for (u64 step = 0; step < slots; ++step, slot = (slot + 1) & (slots - 1)) {
-        const u32 row = slot_rows[slot];
-        if (row >= table.n) break; // empty
-        if (same_key(key_of<E>(table, row), key)) {
-          found = row;
-          break;
-        }
-      }
-    }
+    if (active) found = find_row<E>(slot_rows, slots, table, key_of<E>(lookups, i));
     const bool hit = found != kEmptySlot;
     if constexpr (kLds) {
       if (hit) atomicAdd(bins + found, 1u);
@@ -272,11 +203,6 @@ __global__ void __launch_bounds__(kCountThreads)
 //--------------------------------------------------------------------------------------------------
 // launch geometry
 //--------------------------------------------------------------------------------------------------
-u32 blocks_for(u64 rows, u32 most) {
-  const u64 blocks = (rows + kCountThreads - 1) / kCountThreads;
-  return static_cast<u32>(std::min<u64>(most, std::max<u64>(blocks, 1)));
-}
-
 range_walk walk_of(const sumcheck_column& lookups) {
   const uintptr_t address = reinterpret_cast<uintptr_t>(lookups.data);
   if (lookups.nbytes > 2 || address % lookups.nbytes != 0) return {0, 0};

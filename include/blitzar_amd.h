@@ -749,6 +749,65 @@ void bzamd_count_multiplicities_device(void* multiplicities, void* misses, unsig
  * element.  The hash is NOT part of the ABI and may change between versions. */
 uint64_t bzamd_multiplicity_first_slot(unsigned field_id, const void* element, uint64_t table_rows);
 
+/* Sums of value columns by key: the result columns of a group-by, and the match index of a join.
+ * Per key of the table, the sum of each value column over the input rows that carry the key and
+ * their number, so that for every value column v
+ *   sum_t sums_v[t] / (alpha + T[t]) = sum_i value_v[i] / (alpha + L[i])      whenever misses = 0.
+ * Keys, the equality of rows, first(t), the range table (table.data == NULL), `misses` and the
+ * limits 1 <= m <= 2^28, 0 <= n <= 2^30 are those above bzamd_count_multiplicities.  The value
+ * columns mean what they mean in bzamd_combine_columns and are validated by the same rule:
+ * element_nbytes 1 .. 31 little-endian integers, two's complement when is_signed (up to 16 bytes);
+ * element_nbytes 32 the field's elements, unreduced values included, Montgomery words in field 1;
+ * data at any address; values[v].n <= n rows (longer aborts), rows past a column's end are zero.
+ * The value of a row is its value in the field: a negative x is p - |x|.
+ *   sums:    num_values x m x 32 bytes, column v at sums + 32 m v, element form, canonical:
+ *              sums_v[t] = sum over {i < n : key(L[i]) = key(T[t])} of value_v[i]  mod p
+ *            when first(t) = t; 0 otherwise, and 0 for a key nobody looks up.
+ *   scalars: the same shape, the same rows in scalar form, what bzamd_msm_device reads as a
+ *            32-byte column (the two forms are defined above bzamd_fold_polynomial).
+ *   counts:  m x 8 bytes: exactly the `multiplicities` of bzamd_count_multiplicities for the same
+ *            table and lookups.
+ *   misses:  one uint64_t, as in bzamd_count_multiplicities.
+ *   matches: n x 4 bytes, little-endian uint32_t, 4-byte aligned: matches[i] = first(t) of the
+ *            table row that L[i] hits, 0xFFFFFFFF for a miss; with the range table the key itself
+ *            when it is below m.
+ * Any output may be NULL: with num_values = 0 both sums and scalars must be; with num_values >= 1
+ * at least one of them must not be; at least one output must not be.  Lookups that miss contribute
+ * nowhere.  No input is written.  The result is the same bits from run to run.
+ * 0 <= num_values <= 8; field_id 0 or 1.  Aborts, before anything is launched: a null k, a null
+ * values with num_values > 0, a bad descriptor, a value column longer than n, a limit exceeded, a
+ * misaligned output (8 bytes; matches 4), an output that overlaps an input, another output or the
+ * workspace, a workspace that is too small, an unsupported field id, the device form on the cpu
+ * backend. */
+struct bzamd_key_sums {
+  struct sxt_sequence_descriptor table;   /* m = table.n rows; data NULL: the range table T[t] = t */
+  struct sxt_sequence_descriptor lookups; /* n = lookups.n rows: the key of every input row */
+  const struct sxt_sequence_descriptor* values; /* num_values descriptors, values[v].n <= n */
+  unsigned num_values;                    /* 0 .. 8 */
+};
+/* What the device form's workspace takes: the slots of bzamd_count_multiplicities_workspace_bytes
+ * padded to a multiple of 256, 64 bytes per table row and value column (eight 64-bit accumulators,
+ * what the widest column needs), and 256 bytes for the pointer's alignment.  Needs no backend;
+ * 0 outside 1 <= table_rows <= 2^28, num_values <= 8. */
+uint64_t bzamd_sum_by_key_workspace_bytes(uint64_t table_rows, unsigned num_values);
+/* HOST operands (every descriptor's data included), blocking, cpu and gpu backends.  The cpu backend
+ * goes row by row with one field addition per row and value column; the gpu backend uploads the
+ * columns at their own width, runs the device form on memory of the call's own, synchronises once
+ * and downloads the outputs. */
+void bzamd_sum_by_key(void* sums, void* scalars, void* counts, uint64_t* misses, void* matches,
+                      unsigned field_id, const struct bzamd_key_sums* k);
+/* DEVICE pointers on the current HIP device: the five outputs, workspace, table.data, lookups.data
+ * and every values[v].data (read in stream order, never written).  HOST: the struct and the value
+ * descriptors, which are read before the call returns.  gpu backend only (anything else aborts).
+ * The call only enqueues on `stream`: no synchronise, no allocation, no callback.  FOUR kernel
+ * launches (the range table: THREE), whatever m, n, num_values and the data are.  workspace: at
+ * least bzamd_sum_by_key_workspace_bytes(m, num_values) bytes at any address, contents ignored (the
+ * range table with num_values = 0 needs none: NULL); a later call on the same stream may use the
+ * same workspace. */
+void bzamd_sum_by_key_device(void* sums, void* scalars, void* counts, void* misses, void* matches,
+                             unsigned field_id, const struct bzamd_key_sums* k, void* workspace,
+                             uint64_t workspace_bytes, void* stream);
+
 /* The word columns of a range check.  A value is in range when its byte words are: every word is
  * looked up in the table 0 .. 255, and the prover commits to the word columns, the 256 word counts
  * and one inverse column 1 / (alpha + word) per word column.
