@@ -249,6 +249,19 @@ def load():
         lib.bzamd_sum_by_key.restype = None
         lib.bzamd_sum_by_key_device.argtypes = [vp, vp, vp, vp, vp, cu, vp, vp, u64, vp]
         lib.bzamd_sum_by_key_device.restype = None
+    if hasattr(lib, "bzamd_select_rows_device"):
+        lib.bzamd_select_rows_workspace_bytes.argtypes = [u64]
+        lib.bzamd_select_rows_workspace_bytes.restype = u64
+        lib.bzamd_select_rows.argtypes = [vp, vp, vp]
+        lib.bzamd_select_rows.restype = None
+        lib.bzamd_select_rows_device.argtypes = [vp, vp, vp, vp, u64, vp]
+        lib.bzamd_select_rows_device.restype = None
+        lib.bzamd_select_rows_packed_width.argtypes = [ctypes.c_int]
+        lib.bzamd_select_rows_packed_width.restype = ctypes.c_int
+        lib.bzamd_take_rows.argtypes = [vp]
+        lib.bzamd_take_rows.restype = None
+        lib.bzamd_take_rows_device.argtypes = [vp, vp]
+        lib.bzamd_take_rows_device.restype = None
     if hasattr(lib, "bzamd_decompose_words_device"):
         lib.bzamd_decompose_words.argtypes = [vp, vp, vp, cu, vp]
         lib.bzamd_decompose_words.restype = None
@@ -1133,6 +1146,108 @@ def sum_by_key_device(field_id, sums_ptr, scalars_ptr, counts_ptr, misses_ptr, m
         *pointers, field_id, ctypes.byref(k),
         None if workspace_ptr is None else int(workspace_ptr), workspace_bytes,
         None if stream is None else ctypes.c_void_p(int(stream)))
+
+
+class bzamd_row_selection(ctypes.Structure):
+    _fields_ = [("selector", sxt_sequence_descriptor), ("reject", ctypes.c_uint64),
+                ("invert", ctypes.c_int),
+                ("columns", ctypes.POINTER(sxt_sequence_descriptor)),
+                ("selected", ctypes.POINTER(ctypes.c_void_p)), ("num_columns", ctypes.c_uint),
+                ("capacity", ctypes.c_uint64), ("zero_tail", ctypes.c_int)]
+
+
+class bzamd_row_take(ctypes.Structure):
+    _fields_ = [("indices", ctypes.c_void_p), ("num_rows", ctypes.c_uint64),
+                ("columns", ctypes.POINTER(sxt_sequence_descriptor)),
+                ("taken", ctypes.POINTER(ctypes.c_void_p)), ("num_columns", ctypes.c_uint)]
+
+
+def _pointer_array(pointers):
+    ps = [None if p is None else int(p) for p in pointers]
+    return (ctypes.c_void_p * max(1, len(ps)))(*ps)
+
+
+def select_rows_workspace_bytes(n):
+    """bzamd_select_rows_workspace_bytes: no backend needed; 0 outside the limits"""
+    return load().bzamd_select_rows_workspace_bytes(n)
+
+
+def select_rows_packed_width(width=-1):
+    """bzamd_select_rows_packed_width: columns of at most `width` bytes a row are packed in LDS by
+    the device form's second launch (0: none); negative: only ask -> the width in force before"""
+    return load().bzamd_select_rows_packed_width(width)
+
+
+def select_rows(selector, columns=(), reject=0, invert=False, capacity=None, zero_tail=False,
+                want_indices=True):
+    """bzamd_select_rows (host operands, either backend).  selector: one column of 1 .. 8 bytes a
+    row and columns: up to 16 columns, as in combine_columns; capacity: None is the selector's rows
+    -> (count, indices uint32 or None, [uint8 [rows, nbytes] per column]) with rows = capacity
+    with zero_tail, min(count, capacity) without"""
+    selector_descs, keep_selector = make_descriptors(_column_pairs([selector]))
+    descs, keep = make_descriptors(_column_pairs(columns))
+    n, num = int(selector_descs[0].n), len(keep)
+    capacity = n if capacity is None else capacity
+    indices = np.zeros(max(capacity, 1), dtype=np.uint32) if want_indices else None
+    selected = [np.zeros((max(capacity, 1), int(descs[j].element_nbytes)), dtype=np.uint8)
+                for j in range(num)]
+    outputs = _pointer_array(a.ctypes.data for a in selected)
+    count = ctypes.c_uint64(0)
+    s = bzamd_row_selection(selector_descs[0], reject, 1 if invert else 0, descs if num else None,
+                            outputs if num else None, num, capacity, 1 if zero_tail else 0)
+    load().bzamd_select_rows(ctypes.byref(count), _ptr(indices), ctypes.byref(s))
+    del keep_selector, keep
+    rows = capacity if zero_tail else min(int(count.value), capacity)
+    return (int(count.value), None if indices is None else indices[:rows],
+            [a[:rows] for a in selected])
+
+
+def select_rows_device(count_ptr, indices_ptr, selector, columns, selected_ptrs, capacity,
+                       workspace_ptr, workspace_bytes, reject=0, invert=False, zero_tail=False,
+                       stream=None):
+    """bzamd_select_rows_device: enqueue only, two kernel launches.  selector: one
+    (device_ptr, rows, nbytes, signed); columns: a list of such tuples; selected_ptrs: one output
+    pointer per column; every pointer is memory of the current device as an integer (None: a null
+    pointer); `stream` a hipStream_t as an integer (None: the default stream)."""
+    selector_descs, _ = _device_descriptors([selector])
+    descs, num = _device_descriptors(columns)
+    outputs = _pointer_array(selected_ptrs)
+    s = bzamd_row_selection(selector_descs[0], reject, 1 if invert else 0, descs if num else None,
+                            outputs if num else None, num, capacity, 1 if zero_tail else 0)
+    load().bzamd_select_rows_device(
+        None if count_ptr is None else int(count_ptr),
+        None if indices_ptr is None else int(indices_ptr), ctypes.byref(s),
+        None if workspace_ptr is None else int(workspace_ptr), workspace_bytes,
+        None if stream is None else ctypes.c_void_p(int(stream)))
+
+
+def take_rows(indices, columns):
+    """bzamd_take_rows (host operands, either backend).  indices: uint32 [num_rows]; columns: 1 ..
+    16 columns as in combine_columns, of any lengths -> [uint8 [num_rows, nbytes] per column]:
+    row r is row indices[r] of the column, zero bytes where that is past its end"""
+    indices = np.ascontiguousarray(indices, dtype=np.uint32)
+    descs, keep = make_descriptors(_column_pairs(columns))
+    num = len(keep)
+    taken = [np.zeros((max(len(indices), 1), int(descs[j].element_nbytes)), dtype=np.uint8)
+             for j in range(num)]
+    outputs = _pointer_array(a.ctypes.data for a in taken)
+    t = bzamd_row_take(indices.ctypes.data, len(indices), descs, outputs, num)
+    load().bzamd_take_rows(ctypes.byref(t))
+    del keep
+    return [a[:len(indices)] for a in taken]
+
+
+def take_rows_device(indices_ptr, num_rows, columns, taken_ptrs, stream=None):
+    """bzamd_take_rows_device: enqueue only, one kernel launch.  columns: a list of
+    (device_ptr, rows, nbytes, signed); taken_ptrs: one output pointer per column; every pointer
+    is memory of the current device as an integer (None: a null pointer); `stream` a hipStream_t
+    as an integer (None: the default stream)."""
+    descs, num = _device_descriptors(columns)
+    outputs = _pointer_array(taken_ptrs)
+    t = bzamd_row_take(None if indices_ptr is None else int(indices_ptr), num_rows, descs, outputs,
+                       num)
+    load().bzamd_take_rows_device(ctypes.byref(t),
+                                  None if stream is None else ctypes.c_void_p(int(stream)))
 
 
 class bzamd_word_decomposition(ctypes.Structure):

@@ -39,6 +39,7 @@ SOURCES = [
     "proof/column_inverse.hip",
     "proof/multiplicities.hip",
     "proof/key_sums.hip",
+    "proof/select_rows.hip",
     "proof/word_columns.hip",
     "proof/univariate_opening.hip",
     "proof/verify_opening.hip",

@@ -26,6 +26,7 @@
 #include "blitzar_amd/csrc/proof/inner_product.h"
 #include "blitzar_amd/csrc/proof/column_inverse.h"
 #include "blitzar_amd/csrc/proof/key_sums.h"
+#include "blitzar_amd/csrc/proof/select_rows.h"
 #include "blitzar_amd/csrc/proof/mle_opening.h"
 #include "blitzar_amd/csrc/proof/multiplicities.h"
 #include "blitzar_amd/csrc/proof/univariate_opening.h"
@@ -2248,6 +2249,71 @@ void bzamd_sum_by_key_device(void* sums, void* scalars, void* counts, void* miss
   const proof::key_sum_outputs out{sums, scalars, counts, misses, matches};
   proof::check_key_sums(out, field_id, key_sums, workspace, workspace_bytes, true);
   proof::sum_by_key_device(out, field_id, key_sums, workspace, device_form(stream).stream);
+}
+
+namespace {
+// the selection's columns: the selector and the columns checked as in prove_sumcheck_columns_entry.
+// `columns` keeps them alive
+proof::row_selection selection_form(const char* name, const struct bzamd_row_selection* s,
+                                    std::vector<proof::sumcheck_column>& columns) {
+  check_arguments(name, s != nullptr && (s->num_columns == 0 ||
+                                         (s->columns != nullptr && s->selected != nullptr)));
+  BZ_RELEASE_ASSERT(s->num_columns <= proof::kMaxSelectColumns,
+                    "the row selection needs num_columns <= 16");
+  columns = checked_sumcheck_columns(s->columns, s->num_columns);
+  return {checked_sumcheck_columns(&s->selector, 1)[0], s->reject, s->invert != 0, columns.data(),
+          s->selected, s->num_columns, s->capacity, s->zero_tail != 0};
+}
+proof::row_take take_form(const char* name, const struct bzamd_row_take* t,
+                          std::vector<proof::sumcheck_column>& columns) {
+  check_arguments(name, t != nullptr && t->indices != nullptr && t->columns != nullptr &&
+                            t->taken != nullptr);
+  BZ_RELEASE_ASSERT(t->num_columns >= 1 && t->num_columns <= proof::kMaxSelectColumns,
+                    "the row gather needs 1 <= num_columns <= 16");
+  columns = checked_sumcheck_columns(t->columns, t->num_columns);
+  return {t->indices, t->num_rows, columns.data(), t->taken, t->num_columns};
+}
+} // namespace
+
+// selection of rows: compaction by a selector column and gather by index (proof/select_rows.hip).
+// Both forms check their arguments before they ask for the backend
+uint64_t bzamd_select_rows_workspace_bytes(uint64_t n) {
+  return proof::select_rows_workspace_bytes(n);
+}
+
+void bzamd_select_rows(uint64_t* count, void* indices, const struct bzamd_row_selection* s) {
+  std::vector<proof::sumcheck_column> columns;
+  const proof::row_selection selection = selection_form("bzamd_select_rows", s, columns);
+  proof::check_row_selection(count, indices, selection, nullptr, 0, false);
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::select_rows(st, count, indices, selection);
+}
+
+void bzamd_select_rows_device(void* count, void* indices, const struct bzamd_row_selection* s,
+                              void* workspace, uint64_t workspace_bytes, void* stream) {
+  std::vector<proof::sumcheck_column> columns;
+  const proof::row_selection selection = selection_form("bzamd_select_rows_device", s, columns);
+  proof::check_row_selection(count, indices, selection, workspace, workspace_bytes, true);
+  proof::select_rows_device(count, indices, selection, workspace, device_form(stream).stream);
+}
+
+int bzamd_select_rows_packed_width(int width) { return proof::select_rows_packed_width(width); }
+
+void bzamd_take_rows(const struct bzamd_row_take* t) {
+  std::vector<proof::sumcheck_column> columns;
+  const proof::row_take take = take_form("bzamd_take_rows", t, columns);
+  proof::check_row_take(take);
+  api_state& st = state();
+  const api_state::device_lease lease = lease_primary(st);
+  proof::take_rows(st, take);
+}
+
+void bzamd_take_rows_device(const struct bzamd_row_take* t, void* stream) {
+  std::vector<proof::sumcheck_column> columns;
+  const proof::row_take take = take_form("bzamd_take_rows_device", t, columns);
+  proof::check_row_take(take);
+  proof::take_rows_device(take, device_form(stream).stream);
 }
 
 namespace {

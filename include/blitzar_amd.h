@@ -808,6 +808,105 @@ void bzamd_sum_by_key_device(void* sums, void* scalars, void* counts, void* miss
                              unsigned field_id, const struct bzamd_key_sums* k, void* workspace,
                              uint64_t workspace_bytes, void* stream);
 
+/* Selection of rows: the stable compaction of typed columns by a selector column, and the gather
+ * by row index that goes with it.  A WHERE keeps the rows of its result columns whose flag is set;
+ * a group-by needs the dense table of distinct keys (the rows at which the `multiplicities` of
+ * bzamd_count_multiplicities with the key column as table and lookups are non-zero); a join drops
+ * the misses of the `matches` of bzamd_sum_by_key and fetches the table's columns at the hits.
+ * Neither call does field arithmetic: rows are copied at their own width, for either field and
+ * either form.
+ *   kept(i):  (bits(selector[i]) != reject) != invert, i < n = selector.n, where bits is the row's
+ *             element_nbytes (1 .. 8) bytes as a little-endian unsigned integer, zero-extended to
+ *             64 bits; is_signed does not enter.  A u8 flag column with reject = 0 is a WHERE; the
+ *             u64 counts with reject = 0 give first occurrences; the u32 matches with
+ *             reject = 0xFFFFFFFF give the hits, with invert = 1 the misses (anti-join).
+ *   rank(i):  the number of kept rows before i.
+ *   count:    (may be NULL) one uint64_t, 8-byte aligned: the number of kept rows, exact even when
+ *             it exceeds capacity.
+ *   selected: num_columns output pointers, 8-byte aligned each: kept row i of columns[j] goes to
+ *             bytes rank(i) * w_j ..+ w_j of selected[j], w_j = columns[j].element_nbytes
+ *             (1 .. 32), whenever rank(i) < capacity.  A byte copy.  The columns are validated by
+ *             the rule of bzamd_combine_columns; data at any address; columns[j].n <= n (longer
+ *             aborts); a kept row at or past columns[j].n is written as zero bytes; n = 0 with
+ *             data = NULL is a zero column.  Each output is what every columns call reads as a
+ *             column of w_j-byte rows.
+ *   indices:  (may be NULL) capacity x 4 bytes, little-endian uint32_t, 4-byte aligned:
+ *             indices[rank(i)] = i for kept rows with rank(i) < capacity.
+ *   zero_tail = 1: rows min(count, capacity) .. capacity of every output column are written as
+ *             zero bytes and those of indices as 0xFFFFFFFF, so that the commitment, sumcheck and
+ *             combination of an output over `capacity` rows equal those of its `count` rows, and a
+ *             chain stays enqueue-only with a length the host knows beforehand.
+ *   zero_tail = 0: nothing at or past min(count, capacity) is written.
+ * At least one of count, indices and a column must be asked for.  With capacity = 0 the output
+ * pointers may be NULL.  0 <= n <= 2^30 (n = 0 with data = NULL: count = 0, and the tail rule still
+ * applies); 0 <= capacity <= 2^30, which may exceed n; 0 <= num_columns <= 16.  In-place compaction
+ * is NOT supported.  No input is written.  The result is the same bits from run to run.
+ * Aborts, before anything is launched: a null s, a null columns or selected with num_columns > 0,
+ * a bad descriptor, a selector wider than 8 bytes, a column longer than n, a limit exceeded, no
+ * output asked for, a null output pointer with capacity > 0, a misaligned output (8 bytes; indices
+ * 4), an output that overlaps an input, another output or the workspace, a workspace that is too
+ * small, the device form on the cpu backend. */
+struct bzamd_row_selection {
+  struct sxt_sequence_descriptor selector;       /* n = selector.n rows, element_nbytes 1 .. 8 */
+  uint64_t reject;                               /* compared with the row's bits, zero-extended */
+  int invert;                                    /* 0: keep rows != reject; 1: keep rows == reject */
+  const struct sxt_sequence_descriptor* columns; /* num_columns descriptors, columns[j].n <= n */
+  void* const* selected;                         /* num_columns output pointers (host array) */
+  unsigned num_columns;                          /* 0 .. 16 */
+  uint64_t capacity;                             /* rows every output column (and indices) can hold */
+  int zero_tail;                                 /* 1: rows min(count, capacity) .. capacity are zeroed */
+};
+/* What the device form's workspace takes: one 32-bit count per span of rows (at most 2048 spans of
+ * whole tiles of 1024 rows; n = 0 has one) and 256 bytes for the pointer's alignment.  Needs no
+ * backend; 0 outside n <= 2^30. */
+uint64_t bzamd_select_rows_workspace_bytes(uint64_t n);
+/* HOST operands (every descriptor's data and every selected[j] included), blocking, cpu and gpu
+ * backends.  The cpu backend goes row by row; the gpu backend uploads the columns at their own
+ * width, runs the device form on memory of the call's own, synchronises once and downloads the
+ * outputs. */
+void bzamd_select_rows(uint64_t* count, void* indices, const struct bzamd_row_selection* s);
+/* DEVICE pointers on the current HIP device: count, indices, every selected[j], workspace,
+ * selector.data and every columns[j].data (read in stream order, never written).  HOST: the struct,
+ * the descriptors and the array of output pointers, which are read before the call returns.  gpu
+ * backend only (anything else aborts).  The call only enqueues on `stream`: no synchronise, no
+ * allocation, no callback.  TWO kernel launches, whatever n, the columns and the data are, and no
+ * workgroup waits on another.  workspace: at least bzamd_select_rows_workspace_bytes(n) bytes at
+ * any address, contents ignored; a later call on the same stream may use the same workspace. */
+void bzamd_select_rows_device(void* count, void* indices, const struct bzamd_row_selection* s,
+                              void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* A diagnostic, like bzamd_accumulate_form: how the second launch of bzamd_select_rows_device
+ * stores.  Columns of at most `width` bytes a row (0 .. 32; larger counts as 32) have a tile's kept
+ * rows packed in LDS and written as whole 16-byte pieces; wider columns are stored one row a lane.
+ * 0 stores every column one row a lane.  The results are the same bytes either way.  A negative
+ * width changes nothing.  Returns the width in force before; process-wide, needs no backend. */
+int bzamd_select_rows_packed_width(int width);
+
+/* The gather: row r of taken[j] is row indices[r] of columns[j],
+ *   taken[j][r * w_j ..+ w_j] = columns[j][indices[r]]   when indices[r] < columns[j].n,
+ * and zero bytes otherwise: one rule for the 0xFFFFFFFF of `matches`, the zero tail of `indices`
+ * and short columns.  A byte copy at widths 1 .. 32; the columns may have any lengths and are
+ * validated by the rule of bzamd_combine_columns.  indices: num_rows x uint32_t, 4-byte aligned;
+ * outputs 8-byte aligned; 1 <= num_rows <= 2^30; 1 <= num_columns <= 16.  Aborts, before anything
+ * is launched: a null t, indices, columns, taken or output pointer, a bad descriptor, a limit
+ * exceeded, misalignment, an output that overlaps an input or another output, the device form on
+ * the cpu backend.  No input is written. */
+struct bzamd_row_take {
+  const void* indices;                           /* num_rows x uint32_t, 4-byte aligned */
+  uint64_t num_rows;                             /* 1 .. 2^30 */
+  const struct sxt_sequence_descriptor* columns; /* num_columns source columns, any lengths */
+  void* const* taken;                            /* num_columns output pointers (host array) */
+  unsigned num_columns;                          /* 1 .. 16 */
+};
+/* HOST operands, blocking, cpu and gpu backends (the gpu backend uploads the indices and the
+ * columns, runs the device form, synchronises once and downloads the outputs). */
+void bzamd_take_rows(const struct bzamd_row_take* t);
+/* DEVICE pointers on the current HIP device: indices, every taken[j] and every columns[j].data
+ * (read in stream order, never written).  HOST: the struct, the descriptors and the array of
+ * output pointers.  gpu backend only.  Enqueue only: no synchronise, no allocation, no callback, no
+ * workspace.  ONE kernel launch, whatever num_rows, the columns and the data are. */
+void bzamd_take_rows_device(const struct bzamd_row_take* t, void* stream);
+
 /* The word columns of a range check.  A value is in range when its byte words are: every word is
  * looked up in the table 0 .. 255, and the prover commits to the word columns, the 256 word counts
  * and one inverse column 1 / (alpha + word) per word column.
