@@ -1436,7 +1436,7 @@ static __global__ void __launch_bounds__(kGroupSortThreads, 8) // <= 64 VGPRs: f
 // Skewed data (many equal scalars) makes one bucket span many whole segments.  Consecutive lanes
 // of a wavefront whose segments lie entirely inside the same bucket fold their partials with a
 // segmented shuffle reduction (taken only when such a run exists: wave-uniform branch), and only
-// the first lane of the run writes a head: `load_bucket` below applies the same geometric rule,
+// the first lane of the run writes a head: `heads_of` below applies the same geometric rule,
 // so a bucket of m entries costs its consumer m / (64 segments) additions instead of m / segment.
 template <class P> __device__ __forceinline__ P wave_shfl_down(const P& v, u32 delta) {
   static_assert(sizeof(P) % 4 == 0);
@@ -1773,29 +1773,11 @@ __global__ void __launch_bounds__(kAccumulateThreads)
 // complete sum of bucket b of a task: the owner's partial plus the heads of the following
 // segments the bucket extends into.  Whole segments of one wavefront (64 consecutive segments)
 // were folded into the first of them by k_accumulate.
-template <class C>
-__device__ __forceinline__ typename C::point
-load_bucket(const typename C::point* __restrict__ sums, const typename C::point* __restrict__ heads,
-            u32 begin, u32 end, u32 b, u32 seg_log2) {
-  typename C::point v = sums[b];
-  const u32 first = begin >> seg_log2, last = (end - 1) >> seg_log2;
-  const u32 after_whole = end >> seg_log2; // first segment not entirely below `end`
-  u32 s = first + 1;
-  while (s <= last) {
-    v = C::add(v, heads[s]);
-    if (s < after_whole) {
-      const u32 next_wave = (s / 64 + 1) * 64;
-      s = next_wave < after_whole ? next_wave : after_whole;
-    } else {
-      ++s;
-    }
-  }
-  return v;
-}
-
-// The head partials load_bucket visits for a bucket covering sorted entries [begin, end), in
-// closed form: segment first + 1, every multiple of 64 strictly between that and the last whole
-// segment boundary, and the trailing partial segment.
+// The head partials of a bucket covering sorted entries [begin, end), in closed form: segment
+// first + 1 (first = begin >> seg_log2), every multiple of 64 strictly between that and the last
+// whole segment boundary, and the trailing partial segment (a walk from first + 1 that jumps from a
+// whole segment to the next multiple of 64, or to the first segment not entirely below `end`,
+// visits the same ones: k_reduce_compact).
 struct bucket_heads {
   u32 s0, k_lo, middle, tail_index, count; // indices: s0 | (k_lo + j) * 64, j < middle | tail_index
   __device__ __forceinline__ u32 index(u32 j) const {
@@ -1824,7 +1806,14 @@ __device__ __forceinline__ bucket_heads heads_of(u32 begin, u32 end, u32 seg_log
 // on (8 per lane for a latency-bound launch, up to 64 for a throughput-bound one: plan.h).
 // Running sums over the lane's buckets give s_t = sum B_j and r_t = sum (j + 1) B_j.  The kernel
 // is bound by its total number of point additions (one wavefront per SIMD already keeps the
-// 64-bit multiplier busy), so what matters is how the weights of the lanes are applied:
+// 64-bit multiplier busy).  A bucket's sum is its owner's partial plus its head partials (0, 1 or
+// 2 at 32 entries per bucket and per segment, any number on skewed columns), so the lanes of a
+// wavefront differ in what each bucket costs them: a lane takes its sums, heads and r += s as ONE
+// chain through one addition site (phase 1 below), so that a wavefront pays its longest lane, not
+// the longest lane at every bucket (a walk bucket by bucket -- heads, s += B, r += s at three
+// sites -- issued 31.8 additions per wavefront where this one issues 25.1; every instantiation
+// keeps its wavefronts per SIMD, LDS and zero scratch: DESIGN section 5).  Then what matters is
+// how the weights of the lanes are applied:
 //   * generic: every lane forms (first bucket index) * s_t by double-and-add (~22 operations per
 //     lane), then an LDS tree folds the 256 contributions;
 //   * curves with C::wave_add_multiple (curve25519): the lane weights come from an inclusive
@@ -1899,17 +1888,29 @@ __global__ void __launch_bounds__(T)
   __shared__ point heavy_sum[kReduceMaxHeavy];
   if (tid == 0) heavy_count = 0;
   __syncthreads();
+  u32 chain = 0; // additions of this lane's walk in its chain form (below)
   if (seg_first < nb) {
     const u32 seg_last = seg_first + lane_buckets < nb ? seg_first + lane_buckets : nb;
-    u32 begin = seg_first == 0 ? 0 : ends[seg_first - 1];
+    const u32 lo = seg_first == 0 ? 0 : ends[seg_first - 1];
+    u32 begin = lo;
     for (u32 b = seg_first; b < seg_last; ++b) {
       const u32 end = ends[b];
-      if (end != begin && heads_of(begin, end, seg_log2).count > kReduceHeavyHeads) {
-        const u32 slot = atomicAdd(&heavy_count, 1u);
-        if (slot < kReduceMaxHeavy) heavy_bucket[slot] = b;
+      u32 items = 0; // what the bucket adds into s: its sum and its heads, or its folded sum
+      if (end != begin) {
+        const u32 count = heads_of(begin, end, seg_log2).count;
+        items = 1 + count;
+        if (count > kReduceHeavyHeads) {
+          const u32 slot = atomicAdd(&heavy_count, 1u);
+          if (slot < kReduceMaxHeavy) {
+            heavy_bucket[slot] = b;
+            items = 1;
+          }
+        }
       }
+      chain += items + 1; // ... and r += s
       begin = end;
     }
+    if (begin == lo) chain = 0; // a lane without entries does not walk
   }
   __syncthreads();
   const u32 num_heavy = heavy_count < kReduceMaxHeavy ? heavy_count : kReduceMaxHeavy;
@@ -1934,25 +1935,77 @@ __global__ void __launch_bounds__(T)
   point s = C::identity();
   point r = C::identity();
   bool populated = false;
-  if (seg_first < nb) {
-    const u32 seg_last = seg_first + lane_buckets < nb ? seg_first + lane_buckets : nb;
-    const u32 lo = seg_first == 0 ? 0 : ends[seg_first - 1];
-    const u32 hi = ends[seg_last - 1];
-    if (hi != lo) {
-      populated = true;
-      u32 end = hi;
-      for (u32 b = seg_last; b-- > seg_first;) {
-        const u32 begin = b == 0 ? 0 : ends[b - 1];
-        if (begin != end) {
-          u32 folded = kReduceMaxHeavy;
-          if (num_heavy != 0 && heads_of(begin, end, seg_log2).count > kReduceHeavyHeads) {
-            for (u32 h = 0; h < num_heavy; ++h) folded = heavy_bucket[h] == b ? h : folded;
-          }
-          s = C::add(s, folded < kReduceMaxHeavy ? heavy_sum[folded]
-                                                 : load_bucket<C>(bs, hd, begin, end, b, seg_log2));
+  {
+    // Phase 1 as ONE chain of additions per lane, through one addition site.  From the lane's last
+    // bucket down, the lane's items are: the bucket's sum (or its folded sum from heavy_sum), each of
+    // its head partials in heads_of's order -- all added into s -- and then r += s; an empty bucket
+    // is its r += s alone.  Every trip of the loop takes the lane's next item, whatever kind the
+    // other lanes are at: s is always one operand, the other one is selected (r, or the item
+    // loaded), and so is the destination, so lanes do not diverge over the kind and a wavefront
+    // runs max over its lanes of (sum over buckets of heads + 2) additions, not the sum over bucket
+    // positions of the maximum.  (2^20 uniform 16-bit digits, 32-entry segments, 8 buckets per lane,
+    // counted on the CPU: 31.8 -> 25.1 additions per wavefront, the lanes' mean being 23.7.)
+    // `chain` counted the lane's items above; lanes that have run out are masked (`live`).
+    u32 trips = chain;
+    for (u32 d = 32; d > 0; d >>= 1) {
+      const u32 o = __shfl_xor(trips, d, 64);
+      trips = o > trips ? o : trips;
+    }
+    trips = __builtin_amdgcn_readfirstlane(trips);
+    const u32 seg_last = seg_first < nb ? (seg_first + lane_buckets < nb ? seg_first + lane_buckets : nb)
+                                        : seg_first;
+    bool live = chain != 0;
+    populated = live;
+    // the current bucket b covers [begin, end): n items go into s, item j is next (j == n: r += s);
+    // `pre` is the begin of bucket b - 1, read one bucket ahead
+    u32 b = 0, begin = 0, end = 0, pre = 0, n = 0, j = 0, folded = kReduceMaxHeavy;
+    bucket_heads list = {};
+    auto enter = [&](u32 bucket, u32 bucket_begin, u32 bucket_end) {
+      b = bucket;
+      begin = bucket_begin;
+      end = bucket_end;
+      pre = b > seg_first && b > 1 ? ends[b - 2] : 0;
+      j = 0;
+      n = 0;
+      folded = kReduceMaxHeavy;
+      if (begin != end) {
+        list = heads_of(begin, end, seg_log2);
+        n = 1 + list.count;
+        if (num_heavy != 0 && list.count > kReduceHeavyHeads) {
+          for (u32 h = 0; h < num_heavy; ++h) folded = heavy_bucket[h] == b ? h : folded;
+          if (folded < kReduceMaxHeavy) n = 1;
         }
-        r = C::add(r, s);
-        end = begin;
+      }
+    };
+    if (live) {
+      const u32 top = seg_last - 1;
+      enter(top, top == 0 ? 0 : ends[top - 1], ends[top]);
+    }
+#pragma unroll 1
+    for (u32 trip = 0; trip < trips; ++trip) {
+      const bool to_r = j == n;
+      point other = r;
+      if (live && !to_r) {
+        if (num_heavy != 0 && folded < kReduceMaxHeavy) {
+          other = heavy_sum[folded];
+        } else {
+          const point* item = j == 0 ? bs + b : hd + list.index(j - 1);
+          other = *item;
+        }
+      }
+      const point out = C::add(s, other);
+      if (live) {
+        if (to_r) {
+          r = out;
+          if (b == seg_first) {
+            live = false;
+          } else {
+            enter(b - 1, pre, begin);
+          }
+        } else {
+          s = out;
+          ++j;
+        }
       }
     }
   }
@@ -2130,7 +2183,7 @@ __global__ void __launch_bounds__(kReduceThreads)
       const u32 begin = valid ? (b == 0 ? 0 : ends[b - 1]) : 0;
       const bool nonempty = valid && begin != end;
       point v = C::identity();
-      u32 hs = 1, hlast = 0, after_whole = 0; // the head partials load_bucket would visit
+      u32 hs = 1, hlast = 0, after_whole = 0; // the head partials of the bucket (heads_of), as a walk
       if (nonempty) {
         u32 folded = kReduceMaxHeavy;
         if (num_heavy != 0 && heads_of(begin, end, seg_log2).count > kReduceHeavyHeads) {
